@@ -1,6 +1,14 @@
 """Benchmark: SGP iterations/s (fp64) on batched 256x256 images + %HBM peak.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|c4|c5] ...
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line
+(`value`, `ms_per_step` = wall time of the K timed steps / K); --dump-outputs
+DIR then also writes what the last timed step returned (dump_outputs below).
+Everything else described here (roofline, traffic, end_to_end, cpu_baseline;
+app375's multistart) is a run of its own after the timed steps and needs
+--full; without it those fields are null.
 
 A *step* is one complete batched solve (BASELINE config C3: 1024 independent
 256x256 star-field stamps per GPU, beta-SGP, fp64, 25x25 Gaussian PSF with the
@@ -187,11 +195,20 @@ def synth_batch(B, n, k, nstars, seed0, bkg=100.0, circular=False):
                           else _bsgp.BSGP_CONV_LINEAR_FILL)
     pos = np.empty((B, nstars), dtype=np.int64)
     flx = np.empty((B, nstars))
+    acc = np.zeros(n * n)
     for i in range(B):
         rng = np.random.default_rng(seed0 + i)
         p = rng.integers(0, n, (nstars, 2))
-        pos[i] = p[:, 0] * n + p[:, 1]
-        flx[i] = rng.pareto(1.5, nstars) * 1000 + 100
+        q = p[:, 0] * n + p[:, 1]
+        # stars that share a pixel are summed here, in their order, and the
+        # row is padded with zero fluxes: the device's scatter_add_ then adds
+        # one value per pixel and the image does not depend on the order of
+        # its atomics (the same inputs in every run, --dump-outputs)
+        np.add.at(acc, q, rng.pareto(1.5, nstars) * 1000 + 100)
+        u = np.unique(q)
+        pos[i], flx[i] = u[0], 0.0
+        pos[i, :u.size], flx[i, :u.size] = u, acc[u]
+        acc[u] = 0.0
     obj = torch.zeros(B, n * n, dtype=torch.float64, device="cuda")
     obj.scatter_add_(1, torch.from_numpy(pos).cuda(), torch.from_numpy(flx).cuda())
     blurred = plan.apply(obj.view(B, n, n)).clamp_min(0)
@@ -373,8 +390,10 @@ def bench_app375(args):
     kw1 = dict(kw, betaParam=betas[0])
     for _ in range(max(1, args.warmup)):
         sgp.sgp_betaDiv(img, psf, bkg, **kw1)
-        sgp.sgp_betaDiv_multistart(img, psf, bkg, betas=betas, **kw)
+        if args.full:
+            sgp.sgp_betaDiv_multistart(img, psf, bkg, betas=betas, **kw)
     torch.cuda.synchronize()
+    last = {}
 
     def timed(fn):
         walls, spans, its = [], [], []
@@ -390,12 +409,22 @@ def bench_app375(args):
             its.append(r)
         return float(np.median(walls)), float(np.median(spans)), its[-1]
 
-    w1, g1, it1 = timed(lambda: sgp.sgp_betaDiv(img, psf, bkg, **kw1)[1])
+    def one():
+        last["x"], last["iters"], last["discr"] = sgp.sgp_betaDiv(img, psf, bkg, **kw1)[:3]
+        return last["iters"]
+    w1, g1, it1 = timed(one)
+    if args.dump_outputs:  # the drop-in's return values of the last timed call
+        write_arrays(args.dump_outputs, last)
 
     def ms():
         _, info = sgp.sgp_betaDiv_multistart(img, psf, bkg, betas=betas, **kw)
         return sum(c[1] for c in info["candidates"])
-    wm, gm, itm = timed(ms)
+    multistart = None
+    if args.full:
+        wm, gm, itm = timed(ms)
+        multistart = {"what": "sgp_betaDiv_multistart: the five seeds as one batched launch",
+                      "candidate_iterations": int(itm), "ms": wm * 1e3, "gpu_span_ms": gm * 1e3,
+                      "value": itm / wm, "unit": "candidate iterations/s"}
     res = {
         "metric": "SGP iterations/sec (fp64) of the drop-in on one 375x375 float32 subdivision "
                   "(the application's call shape)",
@@ -410,13 +439,11 @@ def bench_app375(args):
                                "init_recon=2, stop_criterion=3 (tol 1e-5), beta fixed (seed 0)",
                    "iterations": int(it1), "gpu_span_ms": g1 * 1e3,
                    "host_share": 1.0 - g1 / w1},
-        "multistart": {"what": "sgp_betaDiv_multistart: the five seeds as one batched launch",
-                       "candidate_iterations": int(itm), "ms": wm * 1e3, "gpu_span_ms": gm * 1e3,
-                       "value": itm / wm, "unit": "candidate iterations/s"},
+        "multistart": multistart,
         "context": PUBLISHED_CONTEXT["sub375"],
         "roofline": None, "cpu_baseline": None,
     }
-    if not args.no_profile:
+    if args.full and not args.no_profile:
         import _bsgp
         g = torch.from_numpy(np.asarray(img, dtype=np.float32).copy()).cuda()[None]
         b = torch.from_numpy(np.asarray(bkg, dtype=np.float64)).cuda()[None]
@@ -434,7 +461,7 @@ def bench_app375(args):
             "us_per_iteration": {n_: float(kms[i] / max(it, 1) * 1e3) for i, n_ in enumerate(names)
                                  if i > 0 and nl[i] > 0},
             "profiled_solve_ms": float(np.sum(kms))}
-    if not args.no_cpu:
+    if args.full and not args.no_cpu:
         import sgp_oracle
         t0 = time.perf_counter()
         _, ito, _, _, _ = sgp_oracle.sgp_betaDiv(img, psf, bkg, **kw1)
@@ -519,11 +546,19 @@ def parse_args(argv=None):
                          "kernels per iteration (default: sgp.PERSIST_DEFAULT)")
     ap.add_argument("--stop3", action="store_true",
                     help="stop rule 3 (tol 1e-5, the application's) instead of stop rule 1")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the secondary measurements: the "
+                         "profiled solve (roofline), the end-to-end solve, the CPU baseline "
+                         "(app375: the multistart timing too); a plain run reports them as null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float64; "
+                         "a fixed, seeded sample of the images when the outputs exceed the "
+                         "size budget)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-e2e", action="store_true",
-                    help="skip the end-to-end solve (host inputs -> host outputs)")
+                    help="with --full: skip the end-to-end solve (host inputs -> host outputs)")
     ap.add_argument("--no-profile", action="store_true",
-                    help="skip the profiled solve (per-kernel roofline)")
+                    help="with --full: skip the profiled solve (per-kernel roofline)")
     ap.add_argument("--cpu-images", type=int, default=16)
     ap.add_argument("--cpu-maxit", type=int, default=None,
                     help="iterations per CPU-baseline image (default: --maxit)")
@@ -708,6 +743,8 @@ def main():
         return
 
     import sgp
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out)
     cnt = out["counters"].cpu().numpy()
     kern_ms = float(np.mean([a.elapsed_time(b) for a, b in ev]))
     persistent = kw["persistent"] if kw["persistent"] is not None else sgp.PERSIST_DEFAULT
@@ -723,11 +760,12 @@ def main():
                              "gn_compact": sgp.GN_COMPACT_DEFAULT, "storage": args.storage,
                              "persistent": persistent,
                              "stop_criterion": kw["stop_criterion"]})
-    if not args.no_profile:
+    # the secondary measurements, each a run of its own after the timed steps
+    if args.full and not args.no_profile:
         result["roofline"] = roofline(args, kw, gn, psf, bkg, B, n, kern_ms)
-    if not args.no_e2e:
+    if args.full and not args.no_e2e:
         result["end_to_end"] = end_to_end(kw, gn, psf, bkg)
-    if world == 1 and not args.no_cpu:
+    if args.full and world == 1 and not args.no_cpu:
         workers = max(1, min(CPU_CAP, os.cpu_count() or 1))
         images = args.cpu_images if B > 1 else 1
         cpu_maxit = args.cpu_maxit if args.cpu_maxit else args.maxit
@@ -738,6 +776,36 @@ def main():
             result["cpu_baseline"] = cpu_baseline(n, k, nstars, images, cpu_maxit,
                                                   min(workers, images), circular=circ)
     print(json.dumps(result), flush=True)
+
+
+DUMP_BUDGET = 48 << 20  # bytes of the sampled arrays of --dump-outputs (the whole dump < 64 MB)
+
+
+def write_arrays(d, arrays):
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        a = a.cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
+def dump_outputs(d, out, seed=0):
+    """--dump-outputs: what the last timed step handed to its caller, as
+    float64 DIR/<name>.npy: the restored images `x`, their discrepancy
+    series `discr` (zero past an image's last iteration), the iteration
+    counts `iters` and the final beta `beta_final` (rank 0's shard under
+    --gpus N).  When x and discr of the whole batch exceed DUMP_BUDGET they
+    are written for a sample of the images, drawn without replacement by a
+    generator of fixed seed and sorted, whose indices are `images`; iters and
+    beta_final are always whole.  The inputs are seeded, so two runs with the
+    same arguments dump the outputs of the same solves."""
+    x, discr = out["x"], out["discr"]
+    B = x.shape[0]
+    per_image = (x[0].numel() + discr.shape[1]) * 8
+    m = max(1, min(B, DUMP_BUDGET // per_image))
+    idx = np.arange(B) if m == B else np.sort(np.random.default_rng(seed).choice(B, m, replace=False))
+    sel = torch.from_numpy(idx).to(x.device)
+    write_arrays(d, {"images": idx, "x": x[sel], "discr": discr[sel], "iters": out["iters"],
+                     "beta_final": out["beta_final"]})
 
 
 def end_to_end(kw, gn, psf, bkg):

@@ -2,6 +2,7 @@
 # Interleaved A/B/... benchmark, REPS rounds, median per variant.
 # Usage: bash scripts/gpu_ab.sh TAG REPS spec... [-- common bench args]
 #   spec = LIB[,extra,bench,args][,NAME=VALUE env]   LIB "base" = libbsgp.so, else libbsgp_LIB.so
+#   the per-kernel column needs --full among the common bench args (a plain run has no roofline)
 set -o pipefail
 TAG=$1; REPS=$2; shift 2
 SPECS=()

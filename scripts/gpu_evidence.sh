@@ -22,7 +22,7 @@ F=$(find $O/pmc_FETCH_SIZE -name "*counter_collection.csv" | head -1)
 W=$(find $O/pmc_WRITE_SIZE -name "*counter_collection.csv" | head -1)
 python tools/traffic_from_pmc.py $F $W profiles/traffic_c3.json "bench.py (C3), lease $TAG" || exit 3
 cp profiles/traffic_c3.json $O/traffic_c3.json
-timeout -k 10 500 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_c3.json 2> $O/bench_c3.err || { echo "bench failed"; tail -5 $O/bench_c3.err; exit 3; }
+timeout -k 10 500 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_c3.json 2> $O/bench_c3.err || { echo "bench failed"; tail -5 $O/bench_c3.err; exit 3; }
 python -c "import json;d=json.load(open('$O/bench_c3.json'));r=d['roofline'];print('C3', round(d['value']), 'ms', round(d['ms_per_step'],1), 'frac', round(r['frac'],3), 'traffic', r['traffic'], 'k_persist ms', round(r['ms_per_launch'],1), 'cpu', round(d['cpu_baseline']['value']))"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu --no-e2e > $O/prof.log 2>&1 || { echo "prof failed"; exit 3; }
 find $O/prof -name "*kernel_stats.csv" | head -1 | xargs -r cut -d, -f1-4 | grep -E "Name|k_persist"
@@ -38,6 +38,6 @@ for C in "$P1" "$P2"; do
 done
 for cfg in "stamps31" "stamps31_kl" "app375" "sub375" "sub450" "c5" "c2" "c4 --storage f32" "c4"; do
   name=$(echo $cfg | tr ' ' '_' | tr -d '-')
-  timeout -k 10 400 python bench.py --config $cfg > $O/bench_$name.json 2> $O/bench_$name.err || { echo "bench $cfg failed"; tail -5 $O/bench_$name.err; exit 3; }
+  timeout -k 10 400 python bench.py --full --config $cfg > $O/bench_$name.json 2> $O/bench_$name.err || { echo "bench $cfg failed"; tail -5 $O/bench_$name.err; exit 3; }
   python -c "import json;d=json.load(open('$O/bench_$name.json'));r=d['roofline'] or {};c=d.get('cpu_baseline') or {};print('$name', round(d['value']), 'frac', round(r.get('frac') or 0,3), 'solve', round((r.get('solve') or {}).get('frac_timed',0),3), 'cpu', round(c.get('value') or 0,1))"
 done

@@ -8,7 +8,7 @@ O=gpurun_out/$TAG
 CFGS=("$@"); [ ${#CFGS[@]} -eq 0 ] && CFGS=("c3" "c2" "c4 --storage f32" "c4" "sub375")
 for cfg in "${CFGS[@]}"; do
   name=$(echo $cfg | tr ' ' '_' | tr -d '-')
-  timeout -k 10 300 python bench.py --no-cpu --config $cfg > $O/bench_$name.json 2> $O/bench_$name.err || { echo "bench $cfg failed"; tail -5 $O/bench_$name.err; exit 3; }
+  timeout -k 10 300 python bench.py --full --no-cpu --config $cfg > $O/bench_$name.json 2> $O/bench_$name.err || { echo "bench $cfg failed"; tail -5 $O/bench_$name.err; exit 3; }
   python - $O/bench_$name.json $name <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1])); r = d.get("roofline") or {}
