@@ -30,8 +30,9 @@ int fail(int code, const std::string& msg) {
 }
 
 // A/B override knobs (BSGP_PERWAVE_MIN_WG, BSGP_PERWAVE_TW, BSGP_COOP_ELEMS,
-// BSGP_SPIN_LIMIT): a value that is not a whole decimal number in [lo, hi]
-// is ignored and the compiled default used, so a typo cannot turn into a
+// BSGP_FOLD_SETUP, BSGP_SPIN_LIMIT; environment variables, the default is the
+// literal at the call): a value that is not a whole decimal number in [lo, hi]
+// is ignored and the default used, so a typo cannot turn into a
 // zero (a spin limit of 0 fails every persistent solve with a timeout).
 long long env_knob(const char* name, long long def, long long lo, long long hi) {
   const char* e = getenv(name);
@@ -385,9 +386,8 @@ int bsgp_plan_create_checked(int32_t H, int32_t W, const double* psf, int32_t kh
     g.Q = next_fast_len(qmin);
   }
   g.Qh = g.Q / 2 + 1;
-  // stored half spectrum: column k at k * sld (BSGP_SPEC_PAD rows of padding
-  // break a power-of-two column stride; even, so row pairs stay 32-B aligned)
-  g.sld = H + ((H & 1) ? 1 : 0) + BSGP_SPEC_PAD;
+  // stored half spectrum: column k at k * sld (even, so row pairs stay 32-B aligned)
+  g.sld = H + ((H & 1) ? 1 : 0);
   g.fp.n = g.P;
   g.fq.n = g.Q;
   if (!plan_radices(g.P, g.fp.radix, &g.fp.ns) || !plan_radices(g.Q, g.fq.radix, &g.fq.ns)) {
@@ -407,15 +407,19 @@ int bsgp_plan_create_checked(int32_t H, int32_t W, const double* psf, int32_t kh
   // per-wave transforms at three workgroups per CU (12 waves/CU) before the
   // cooperative build's one 512-thread workgroup per CU (8 waves): 375^2 tiles
   // on their 400-point grid fit (52.9 KB of 54.3 KB)
-  // With BSGP_PERWAVE_TW the twiddle tables must fit beside the buffers too:
+  // The twiddle tables must fit beside the buffers too (BSGP_PERWAVE_TW=0: not):
   // a wave's transform that reads its twiddles from global memory waits on
   // them in every stage (375^2 tiles at 3 WG/CU: the 400-point row and column
   // transforms took 3.5x the cycles per point of C3's 270-point ones, phase
   // profile), so two workgroups per CU with LDS twiddles can beat three without.
   const size_t twb_all = (size_t)(g.P == g.Q ? g.P : g.P + g.Q) * sizeof(cd);
   {
-    const int min_wg = (int)env_knob("BSGP_PERWAVE_MIN_WG", BSGP_PERWAVE_MIN_WG, 2, 4);
-    const size_t tw_need = env_knob("BSGP_PERWAVE_TW", BSGP_PERWAVE_TW, 0, 1) ? twb_all : 0;
+    // plans whose per-wave transforms fit the LDS at three or two workgroups
+    // per CU take them instead of the cooperative build when this allows.
+    // Per-wave over cooperative (A/B): 375^2 tiles at 3 WG/CU, 1024 per launch,
+    // 68.6 k -> 87.5 k image-it/s; 450^2 at 2 WG/CU 48.3 -> 59.7 k
+    const int min_wg = (int)env_knob("BSGP_PERWAVE_MIN_WG", 2, 2, 4);
+    const size_t tw_need = env_knob("BSGP_PERWAVE_TW", 1, 0, 1) ? twb_all : 0;
     for (int wg = 3; wg >= 2 && wg >= min_wg; --wg) {
       const size_t bw = 160 * 1024 / wg - 256;
       if (need(kWaves) > budget && need(kWaves) + tw_need <= bw) {
@@ -441,15 +445,16 @@ int bsgp_plan_create_checked(int32_t H, int32_t W, const double* psf, int32_t kh
     // holds, each at least two waves and covering its transform in one load
     // batch (4 elements per thread); the 400/480-point grids take four.  A
     // transform too long for that (C4's 2048 points) takes two groups of
-    // 256 threads with two load batches (BSGP_COOP_ELEMS = 8) when the LDS
+    // 256 threads with two load batches (BSGP_COOP_ELEMS, 8 per thread) when the LDS
     // holds both: each workgroup then runs two row pairs through the same
     // stages and barriers, and its radix-8 stages use all 512 lanes instead
     // of 256: C4 k_ls 180 -> 157 us, k_bb 72 -> 68 us, 2114 -> 2221 it/s
     // (float32 storage; f64 1868 -> 1971), the column kernel staying on one
     // group (nfc below).
-    const int elems = (int)env_knob("BSGP_COOP_ELEMS", BSGP_COOP_ELEMS, 4, 8);  // (A/B override)
+    // elements per thread a group may take when one batch leaves one group
+    const int elems = (int)env_knob("BSGP_COOP_ELEMS", 8, 4, 8);  // (A/B override)
     auto groups = [&](int el) {
-      for (int n = BSGP_COOP_GROUPS; n > 1; n /= 2)
+      for (int n = kCoopGroups; n > 1; n /= 2)
         if (need(n) <= budget && kCoopBlock / n >= 128 && maxlen <= el * (kCoopBlock / n))
           return n;
       return 1;
@@ -461,14 +466,12 @@ int bsgp_plan_create_checked(int32_t H, int32_t W, const double* psf, int32_t kh
     budget = 160 * 1024 / p->wg_per_cu - 256;
   }
   g.nfw = nfw;
-  // the column kernel of a cooperative plan: BSGP_COOP_COLGROUPS groups (0: as the
-  // other kernels), so it may fit more workgroups per CU than they do
-  // (the column kernel keeps one load batch per thread: a 2048-point column per
-  // 256-thread group doubled C4's k_col, 42 -> 75 us, while the row passes gained)
+  // the column kernel of a cooperative plan keeps one load batch per thread: a
+  // 2048-point column per 256-thread group doubled C4's k_col, 42 -> 75 us,
+  // while the row passes gained
   int nfc = nfw;
   while (g.coop && nfc > 1 && maxlen > 4 * (kCoopBlock / nfc)) nfc /= 2;
-  g.nfc = (g.coop && BSGP_COOP_COLGROUPS > 0 && BSGP_COOP_COLGROUPS < nfc) ? BSGP_COOP_COLGROUPS
-                                                                            : nfc;
+  g.nfc = nfc;
   p->lds_fft_bytes = (size_t)nfw * 2 * g.lpad * sizeof(cd);
   p->lds_bytes = p->lds_fft_bytes + red_bytes;
   // the per-wave transforms' twiddle tables live in LDS when they fit the same
@@ -485,23 +488,21 @@ int bsgp_plan_create_checked(int32_t H, int32_t W, const double* psf, int32_t kh
   // and, after them, the 2048-point column transforms' stage tables
   // (bsgp_fft.hpp TwMixL: 9 KiB, the global table's entries for the second and
   // third Stockham stages; loaded by every kernel with the two-level tables)
-  if (g.coop && (BSGP_COOP_TW2 || BSGP_COL_TWMIX)) {
+  if (g.coop) {
     size_t off = 0;
-    if (BSGP_COOP_TW2) {
+    if (g.P == 2048) {
+      g.fp.lds_tw2 = 0;
+      off += (64 + 2048 / 64) * sizeof(cd);
+    }
+    if (g.Q == 2048) {
       if (g.P == 2048) {
-        g.fp.lds_tw2 = 0;
+        g.fq.lds_tw2 = 0;
+      } else {
+        g.fq.lds_tw2 = (int)off;
         off += (64 + 2048 / 64) * sizeof(cd);
       }
-      if (g.Q == 2048) {
-        if (g.P == 2048) {
-          g.fq.lds_tw2 = 0;
-        } else {
-          g.fq.lds_tw2 = (int)off;
-          off += (64 + 2048 / 64) * sizeof(cd);
-        }
-      }
     }
-    if (BSGP_COL_TWMIX && !BSGP_COL_TW2 && g.P == 2048) {
+    if (g.P == 2048) {
       g.twmix = (int)off;
       off += (64 + 512) * sizeof(cd);
     }
@@ -522,8 +523,7 @@ int bsgp_plan_create_checked(int32_t H, int32_t W, const double* psf, int32_t kh
         ncu > 0)
       p->ncu = ncu;
   }
-  if (BSGP_COOP512 && (bsgp_c512_args_size() != sizeof(SolveArgs) ||
-                       bsgp_c512_block() != kCoopBlock)) {
+  if (bsgp_c512_args_size() != sizeof(SolveArgs) || bsgp_c512_block() != kCoopBlock) {
     delete p;
     return fail(BSGP_ERR_HIP, "cooperative 512-thread build does not match this library");
   }
@@ -622,7 +622,7 @@ int bsgp_plan_create_checked(int32_t H, int32_t W, const double* psf, int32_t kh
   p->storage = storage;
   // slot: gn and bkg in float64 (vec_stride each), the seven iteration vectors
   // in the storage type, then the half spectrum (complex float64)
-  p->vec_stride = round_up(N, 32) + BSGP_VEC_PAD;
+  p->vec_stride = round_up(N, 32);
   const size_t vbytes = storage == BSGP_STORAGE_F32 ? sizeof(float) : sizeof(double);
   p->spec_off = 2 * p->vec_stride + 7 * p->vec_stride * vbytes / sizeof(double);
   p->slot_stride = p->spec_off + round_up((size_t)g.sld * g.Qh * 2, 32);
@@ -848,17 +848,16 @@ static int solve_impl(bsgp_plan p, int32_t B, const bsgp_params* prm, const bsgp
   a.Tc = T;
   if (T > 1) {
     // (one-group cooperative columns pair column 0 with the Nyquist column)
-    const int ncol = (p->g.coop && p->g.nfc == 1 && BSGP_COL_PAIR_NYQ && p->g.Q % 2 == 0)
+    const int ncol = (p->g.coop && p->g.nfc == 1 && p->g.Q % 2 == 0)
                          ? p->g.Qh - 1
                          : p->g.Qh;
     const int nc = (ncol + p->g.nfc - 1) / p->g.nfc;
     const int want = 4 * p->ncu / B;
     a.Tc = std::max(T, std::min(nc, want));
   }
-  // column passes fused into the row kernels: one-workgroup images always;
-  // teams of per-wave plans as BSGP_FUSE_COL_TEAM says (the team's own waves
-  // run the columns after a team barrier, instead of a k_col launch)
-  a.fuse_col = T == 1 ? BSGP_FUSE_COL : (p->g.coop ? 0 : BSGP_FUSE_COL_TEAM);
+  // one-workgroup images run AT's column pass at the end of k_ls (bit 1);
+  // teams launch k_col for it
+  a.fuse_col = T == 1 ? 2 : 0;
   a.tpart = T > 1 ? p->tpart : nullptr;
   a.tctr = p->tctr;
   a.tfail = reinterpret_cast<int*>(p->tctr + (size_t)B * kTeamWords);
@@ -880,7 +879,7 @@ static int solve_impl(bsgp_plan p, int32_t B, const bsgp_params* prm, const bsgp
     rc = ensure_plist(p, (size_t)B * a.plist_stride);
     if (rc) return rc;
     a.plist = p->plist;
-    if (BSGP_LIST_LDS && T > 1) {
+    if (T > 1) {  // teams keep their projection lists in LDS as far as they fit
       const size_t fit = p->lds_fft_bytes / ((size_t)plan_block(p->g) * 2 * sizeof(double));
       a.list_lds = (int)std::min<size_t>((size_t)a.lcap, fit);
     }
@@ -903,7 +902,7 @@ static int solve_impl(bsgp_plan p, int32_t B, const bsgp_params* prm, const bsgp
   // 375^2 / 450^2 subdivisions) the 512-thread build's thread-group transforms
   // (bsgp_persist_c512.hip); it overlaps the phases of different images itself,
   // so it runs the whole batch as one sub-batch
-  const bool persist = prm->persistent && T == 1 && (!p->g.coop || BSGP_COOP512) && !track;
+  const bool persist = prm->persistent && T == 1 && !track;
   if (persist) S = 1;
   // fixed-length persistent solves run every image's setup as the first task
   // of its chain inside k_persist: the setups of the last images overlap the
@@ -932,7 +931,7 @@ static int solve_impl(bsgp_plan p, int32_t B, const bsgp_params* prm, const bsgp
   // team barrier counters and the timeout word restart at 0 every solve
   HIP_TRY(hipMemsetAsync(p->tctr, 0, p->tctr_bytes, s));
   // flag barriers: every partial slot starts empty
-  if (T > 1 && (T <= BSGP_TEAM_FLAGS || (BSGP_TEAM_HIER && T >= 8)))
+  if (T > 1 && (T <= kTeamFlags || T >= 8))
     HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)p->tpart, kPartEmptyWord,
                               B * kPartBufs * (size_t)(T + 8) * kMaxRed * 2, s));
   hipStream_t ss[bsgp_plan_s::kMaxStreams];
@@ -991,10 +990,10 @@ static int solve_impl(bsgp_plan p, int32_t B, const bsgp_params* prm, const bsgp
   // device (it waits for the event after iteration it - kLook, never for the
   // stream to drain) and stops enqueueing once the host-mapped word carries
   // this solve's seq, i.e. every image has stopped; the iterations queued
-  // past the last stop find every image stopped and return at once.  (Round 4
-  // drained the stream and copied the counter after EVERY iteration for
-  // B <= 4: one host round trip per iteration on the latency-bound
-  // single-image solves.)
+  // past the last stop find every image stopped and return at once.  (Draining
+  // the stream after every iteration, as round 4 did, is one host round trip
+  // per iteration on the latency-bound single-image solves: measured and
+  // removed.)
   const bool data_stop = prm->stop_criterion >= 2 && prm->stop_criterion <= 4;
   constexpr int kLook = 2;
   if (data_stop)
@@ -1008,10 +1007,7 @@ static int solve_impl(bsgp_plan p, int32_t B, const bsgp_params* prm, const bsgp
                                prof ? &prof->ev[2 + 6 * (size_t)(it - 1)] : nullptr));
       if (track) HIP_TRY(launch_track(sa[j], it, ss[j]));
     }
-    if (data_stop && it < prm->MAXIT && !BSGP_POLL_LOOKAHEAD) {  // (A/B: round 4's polling)
-      for (int j = 0; j < S; ++j) HIP_TRY(hipStreamSynchronize(ss[j]));
-      if (__atomic_load_n(p->done_h, __ATOMIC_ACQUIRE) == a.seq) break;
-    } else if (data_stop && it < prm->MAXIT) {
+    if (data_stop && it < prm->MAXIT) {
       HIP_TRY(hipEventRecord(p->ev_it[it % bsgp_plan_s::kPollRing], ss[0]));
       if (it > kLook) {
         HIP_TRY(hipEventSynchronize(p->ev_it[(it - kLook) % bsgp_plan_s::kPollRing]));
@@ -1037,7 +1033,7 @@ static int solve_impl(bsgp_plan p, int32_t B, const bsgp_params* prm, const bsgp
     prof->kernel_ms[0] = ms;
     prof->launches[0] = 1;
     const int cls[5] = {1, 2, 3, 2, 4};
-    const bool launched[5] = {true, !(sa[0].fuse_col & 5), true, !(sa[0].fuse_col & 2), true};
+    const bool launched[5] = {true, true, true, !(sa[0].fuse_col & 2), true};
     for (int it = 0; it < it_run; ++it) {
       hipEvent_t* e = &prof->ev[2 + 6 * (size_t)it];
       for (int k = 0; k < 5; ++k) {

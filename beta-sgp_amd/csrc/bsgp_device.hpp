@@ -27,19 +27,14 @@ constexpr int kWaves = kBlock / 64;
 constexpr int kMaxRed = 24;  // doubles reduced at once
 
 // Team barriers and reductions on per-member words (round 5)
-// for teams of at most BSGP_TEAM_FLAGS members: a member's arrival is one
+// for teams of at most kTeamFlags members: a member's arrival is one
 // store to its own word and its reduction partials are their own arrival
 // flags (slots pre-filled with kPartEmpty, triple-buffered), so a barrier is
 // one store plus the readers' polls instead of the hierarchical counters'
 // chain of atomics.  Every member polls every member, so larger teams (C4's
-// 256) go through eight group leaders (BSGP_TEAM_HIER) or keep the
-// XCD-hierarchical counters; 0 disables the flags (A/B).
-#ifndef BSGP_TEAM_FLAGS
-#define BSGP_TEAM_FLAGS 64
-#endif
-#ifndef BSGP_TEAM_HIER
-#define BSGP_TEAM_HIER 1
-#endif
+// 256) go through eight group leaders (Team::flags 2, teams of 8 and more;
+// measured against the XCD-hierarchical counters, profiles/r05/ab_round5.txt).
+constexpr int kTeamFlags = 64;
 constexpr int kPartBufs = 3;
 // A signalling NaN (hi word == lo word, so hipMemsetD32 can fill it):
 // arithmetic never produces one, and stored partials are canonicalised.
@@ -154,17 +149,14 @@ struct WaveSync {
 // quad permutes (VALU, no LDS pipe), xor 4 / 8 / 16 by ds_swizzle's bit mode
 // (no address VGPR), xor 32 by ds_bpermute (__shfl_xor).  The same pairing as
 // __shfl_xor for every O, so the reduction trees below keep their bits.
-#ifndef BSGP_WAVE_DPP
-#define BSGP_WAVE_DPP 1
-#endif
 template <int O>
 __device__ __forceinline__ double xor_lanes(double v) {
-  if constexpr (BSGP_WAVE_DPP && (O == 1 || O == 2)) {
+  if constexpr (O == 1 || O == 2) {
     constexpr int ctrl = O == 1 ? 0xB1 : 0x4E;  // quad_perm [1,0,3,2] / [2,3,0,1]
     const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), ctrl, 0xF, 0xF, false);
     const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), ctrl, 0xF, 0xF, false);
     return __hiloint2double(hi, lo);
-  } else if constexpr (BSGP_WAVE_DPP && O < 32) {
+  } else if constexpr (O < 32) {
     constexpr int pat = (O << 10) | 0x1F;  // bit mode: and 0x1F, or 0, xor O
     const int lo = __builtin_amdgcn_ds_swizzle(__double2loint(v), pat);
     const int hi = __builtin_amdgcn_ds_swizzle(__double2hiint(v), pat);
@@ -290,7 +282,7 @@ static_assert(kMaxTeam <= 8 * 64, "a group leader polls at most 64 members");
 struct Team {
   int m, T;            // member index, team size
   double* part;        // [3][T + 8][kMaxRed] partial slots of this image (+ group sums)
-  int flags;           // 1: flag barriers (T <= BSGP_TEAM_FLAGS), 2: via group leaders, 0: counters
+  int flags;           // 1: flag barriers (T <= kTeamFlags), 2: via group leaders, 0: counters
   unsigned int* ctr;   // the image's kTeamWords barrier words (monotonic across kernels)
   unsigned int base;   // barriers the team completed before this kernel (same in all members)
   int nb;              // team barriers passed in this kernel
@@ -507,14 +499,12 @@ __device__ __forceinline__ bool red_poll_done(Team& t, bool ok, unsigned int& sp
   if (!t.flags || __all(ok)) return true;
   return !team_spin(t, spins);
 }
-// Wide flag reductions (more than BSGP_RED_POLL_MAX loads per lane: NV + NM
+// Wide flag reductions (more than kRedPollMax loads per lane: NV + NM
 // values of ceil(T / 64) members): poll one value per member, the last one
 // stored, before loading all of them, so a poll round is one load per member.
-#ifndef BSGP_RED_POLL_MAX
-#define BSGP_RED_POLL_MAX 24
-#endif
+constexpr int kRedPollMax = 24;
 __device__ __forceinline__ void red_wait_last(Team& t, const double* slot, int last) {
-  if (!t.flags || (last + 1) * ((t.T + 63) >> 6) <= BSGP_RED_POLL_MAX) return;
+  if (!t.flags || (last + 1) * ((t.T + 63) >> 6) <= kRedPollMax) return;
   unsigned int spins = 0;
   for (;;) {
     bool ok = true;
@@ -830,13 +820,11 @@ __device__ __forceinline__ double team_min(double v, double* red, Team& t) {
   return team_ext<false>(v, red, t);
 }
 
-// x**a for the divergence terms: fast_exp(a*fast_log(x)) (bsgp_math.hpp).  For the
+// x**a for the divergence terms: exp(a*fast_log(x)) (bsgp_math.hpp).  For the
 // exponents of this path (|a| = |beta-1| <~ 1, scaled data so |log x| <~ 20)
 // the error is a few ulp at most, at ~1/2.6 the cost of the general pow();
-// x <= 0 follows pow for the cases the iteration can produce.
-#ifndef BSGP_FAST_EXP
-#define BSGP_FAST_EXP 0  // measured: ocml exp is faster at k_ls's occupancy (A/B -2 %)
-#endif
+// x <= 0 follows pow for the cases the iteration can produce.  (The library's
+// exp, not fast_exp: measured faster at k_ls's occupancy, A/B -2 %.)
 __device__ __forceinline__ double fpow(double x, double a) {
 #ifdef BSGP_VALU_X2  // diagnostic: twice the pow work, same values
   const double x2 = x + 0.0 * a * x;
@@ -844,7 +832,7 @@ __device__ __forceinline__ double fpow(double x, double a) {
   const double r2 = exp(a * fast_log(x2));
   return r1 == r2 ? r1 : r2;
 #else
-  return BSGP_FAST_EXP ? fast_exp(a * fast_log(x)) : exp(a * fast_log(x));
+  return exp(a * fast_log(x));
 #endif
 }
 
@@ -1072,35 +1060,25 @@ __device__ __forceinline__ void coop_row_inv_fwd_1(const Geo& G, const Part& D, 
 // (r2c_split).  C4's 1025 stored columns then make 1024 transforms, two
 // rounds of the column kernel's 512 resident workgroups instead of a third
 // round for one leftover column.
-#ifndef BSGP_COL_PAIR_NYQ
-#define BSGP_COL_PAIR_NYQ 1
-#endif
-// The column transforms' plan: BSGP_COL_TW2 0 (default) keeps them on the
-// global twiddle table, the row passes take the LDS two-level table.  With
-// the LDS table the column kernel needed 168 VGPRs (one 512-thread workgroup
+//
+// The column transforms stay off the LDS two-level twiddle table the row
+// passes take (fft_wide<false> where a thread group runs them).  With the
+// LDS table the column kernel needed 168 VGPRs (one 512-thread workgroup
 // per CU) or spilled at 128; on the global table it keeps two per CU.  C4 A/B
 // (profiles/r05/ab_round5.txt): global columns 1802 it/s, LDS columns at 128
 // VGPRs 1781, at 168 VGPRs 1770, no LDS table anywhere 1700.
-#ifndef BSGP_COL_TW2
-#define BSGP_COL_TW2 0
-#endif
 // (a template flag, not a modified copy of the plan: a copy of FftPlan lived
 // in scratch memory and every stage of k_col read its fields from there)
-// Column transforms: fft_wide's paths, the 2048-point one reading its
-// second and third stages' twiddles from the LDS stage tables (Geo::twmix,
-// loaded by load_tw_lds; bitwise the global table's values).
-#ifndef BSGP_COL_TWMIX
-#define BSGP_COL_TWMIX 1
-#endif
+// Whole-workgroup column transforms: the 2048-point one reads its second and
+// third stages' twiddles from the LDS stage tables (Geo::twmix, loaded by
+// load_tw_lds; bitwise the global table's values), every other length runs
+// the runtime plan.
 // (every cooperative 2048-point plan has the tables: bsgp_plan_create)
 __device__ __forceinline__ cd* col_fft(cd* a, cd* b, const Geo& G, bool inv, int t) {
-  if constexpr (BSGP_COL_TWMIX && !BSGP_COL_TW2) {
-    if (G.fp.n == 2048)
-      return fft_run_static<2048, true, true>(a, b, TwMixL{G.twmix, G.fp.tw}, inv, t, kBlock,
-                                              BlockSync());
-    return fft_run(a, b, G.fp, inv, t, kBlock, BlockSync());
-  }
-  return fft_wide<BSGP_COL_TW2>(a, b, G.fp, inv, t, kBlock, BlockSync());
+  if (G.fp.n == 2048)
+    return fft_run_static<2048, true, true>(a, b, TwMixL{G.twmix, G.fp.tw}, inv, t, kBlock,
+                                            BlockSync());
+  return fft_run(a, b, G.fp, inv, t, kBlock, BlockSync());
 }
 __device__ __forceinline__ void coop_col_pair_nyq(const Geo& G, cd* spec, const cd* tf, cd* a,
                                                   cd* b) {
@@ -1146,7 +1124,7 @@ __device__ __forceinline__ void coop_col_conv_1(const Geo& G, const Part& D, cd*
   const int t = threadIdx.x;
   cd* a = lds;
   cd* b = lds + G.lpad;
-  const bool pair = BSGP_COL_PAIR_NYQ && (G.Q % 2) == 0 && G.Qh > 1;
+  const bool pair = (G.Q % 2) == 0 && G.Qh > 1;
   const int kend = pair ? G.Qh - 1 : G.Qh;
   for (int k = D.gw0; k < kend; k += D.gws) {
     if (pair && k == 0) {
@@ -1400,7 +1378,7 @@ __device__ __forceinline__ void coop_col_conv_g(const Geo& G, const Part& D, cd*
     __syncthreads();
     PH_ADD(29, tq0);
     PH_T(tq1);
-    cd* Z = fft_wide<BSGP_COL_TW2>(a, b, G.fp, false, t, c.nt, BlockSync());
+    cd* Z = fft_wide<false>(a, b, G.fp, false, t, c.nt, BlockSync());
     if (act) {
       for (int p0 = 0; p0 < G.P; p0 += c.nt * kCCH) {
         cd tv[kCCH];
@@ -1414,7 +1392,7 @@ __device__ __forceinline__ void coop_col_conv_g(const Geo& G, const Part& D, cd*
       }
     }
     __syncthreads();
-    cd* Y = fft_wide<BSGP_COL_TW2>(Z, (Z == a) ? b : a, G.fp, true, t, c.nt, BlockSync());
+    cd* Y = fft_wide<false>(Z, (Z == a) ? b : a, G.fp, true, t, c.nt, BlockSync());
     if (act)
       for (int p = t; p < G.H; p += c.nt) col[p] = Y[p];
     __syncthreads();
@@ -1465,7 +1443,7 @@ __device__ __forceinline__ void coop_col_conv(const Geo& G, const Part& D, cd* s
 // PIPE: the operand batch j0 + 64*JCH is issued before batch j0 is computed
 // (two batches in flight per wave instead of one round trip per batch; costs
 // a second set of batch registers outside the FFT).
-template <int JCH = kJCH, bool PF = false, bool COMP = BSGP_FFT_COMPOSITE, bool COOP = false,
+template <int JCH = kJCH, bool PF = false, bool COMP = true, bool COOP = false,
           bool PIPE = false, int PHS = -1, class LD, class MK>
 __device__ __forceinline__ void row_fwd2(const Geo& G, const Part& D, int nrows, int ncols,
                                          int ldim, cd* spec, cd* lds, LD&& ld, MK&& mk) {
@@ -1543,7 +1521,7 @@ __device__ __forceinline__ void row_fwd2(const Geo& G, const Part& D, int nrows,
 template <bool COOP = false, class Prod>
 __device__ __forceinline__ void row_fwd(const Geo& G, const Part& D, int nrows, int ncols, int ldim,
                                         cd* spec, cd* lds, Prod&& prod) {
-  row_fwd2<kJCH, false, BSGP_FFT_COMPOSITE, COOP>(G, D, nrows, ncols, ldim, spec, lds, prod,
+  row_fwd2<kJCH, false, true, COOP>(G, D, nrows, ncols, ldim, spec, lds, prod,
                                                   [](int, int, double v) { return v; });
 }
 
@@ -1609,7 +1587,7 @@ __device__ __forceinline__ void unpack_pair(const Geo& G, const cd* F, bool two,
 // PRE: the first operand batch is issued before the FFT (costs its registers
 // across the FFT).
 // PIPE: as row_fwd2 (batch j0 + 64*JCH in flight while batch j0 is consumed).
-template <bool PRE, int JCH = kJCH, bool COMP = BSGP_FFT_COMPOSITE, bool COOP = false,
+template <bool PRE, int JCH = kJCH, bool COMP = true, bool COOP = false,
           bool PIPE = false, int PHS = -1, class LD, class USE>
 __device__ __forceinline__ void row_inv2(const Geo& G, const Part& D, const cd* spec, cd* lds,
                                          LD&& ld, USE&& use) {
@@ -1683,7 +1661,7 @@ __device__ __forceinline__ void row_inv2(const Geo& G, const Part& D, const cd* 
 template <bool COOP = false, class Cons>
 __device__ __forceinline__ void row_inv(const Geo& G, const Part& D, const cd* spec, cd* lds,
                                         Cons&& cons) {
-  row_inv2<false, kJCH, BSGP_FFT_COMPOSITE, COOP>(
+  row_inv2<false, kJCH, true, COOP>(
       G, D, spec, lds, [](int, int) { return 0; },
       [&](int r, int j, double v, int) { cons(r, j, v); });
 }
@@ -1731,15 +1709,13 @@ __device__ __forceinline__ void row_inv_fwd(const Geo& G, const Part& D, cd* spe
   }
 }
 
-// measured on C3 (A/B): the TF loaded after the forward FFT keeps k_col at
-// 111 VGPRs (4 waves/SIMD) and runs 8 % faster than batching it with the column
-#ifndef BSGP_COL_TFPRE
-#define BSGP_COL_TFPRE false
-#endif
 // col_conv: every wave owns whole columns: it streams stored column k
 // (contiguous, H rows) into its LDS buffer, zero-fills rows H..P-1, runs the
 // forward P-point FFT, multiplies by tf[k][:], runs the inverse FFT and
 // writes rows [0, H) back.  No workgroup barrier inside the pass.
+// The TF is loaded after the forward FFT: measured on C3 (A/B), that keeps
+// k_col at 111 VGPRs (4 waves/SIMD) and runs 8 % faster than batching its
+// loads with the column's.
 template <bool COOP = false>
 __device__ __forceinline__ void col_conv(const Geo& G, const Part& D, cd* spec, const cd* tf,
                                          cd* lds) {
@@ -1751,13 +1727,9 @@ __device__ __forceinline__ void col_conv(const Geo& G, const Part& D, cd* spec, 
   if (w < G.nfw) {
     cd* a = lds + w * 2 * G.lpad;
     cd* b = a + G.lpad;
-    // column and TF loads in one batch before the forward FFT (the TF stays
-    // in registers across it), or the TF loaded after the FFT
-    const bool one = BSGP_COL_TFPRE && G.P <= 64 * kPCH;
     for (int k = D.gw0 + w; k < G.Qh; k += D.gws) {
       cd* col = spec + (size_t)k * G.sld;
       const cd* t = tf + (size_t)k * G.P;
-      cd tv[kPCH];
       for (int p0 = 0; p0 < G.P; p0 += 64 * kPCH) {
         cd cv[kPCH];
 #pragma unroll
@@ -1767,7 +1739,6 @@ __device__ __forceinline__ void col_conv(const Geo& G, const Part& D, cd* spec, 
           const int p = p0 + lane + 64 * u;
           const cd c = col[min(p, G.H - 1)];
           cv[u] = p < G.H ? c : cmk(0.0, 0.0);
-          if (one) tv[u] = t[min(p, G.P - 1)];
         }
 #pragma unroll
         for (int u = 0; u < kPCH; ++u) {
@@ -1777,14 +1748,9 @@ __device__ __forceinline__ void col_conv(const Geo& G, const Part& D, cd* spec, 
       }
       wave_sync();
       cd* Z = fft_any(a, b, G.fp, false, lane, 64, WaveSync());
-      if (one) {
-#pragma unroll
-        for (int u = 0; u < kPCH; ++u) {
-          const int p = lane + 64 * u;
-          if (p < G.P) Z[p] = cmul(Z[p], tv[u]);
-        }
-      } else if (G.P <= 64 * kPCH) {
+      if (G.P <= 64 * kPCH) {
         // the TF column in one load batch after the FFT (one round trip)
+        cd tv[kPCH];
 #pragma unroll
         for (int u = 0; u < kPCH; ++u) tv[u] = t[min(lane + 64 * u, G.P - 1)];
 #pragma unroll

@@ -366,14 +366,11 @@ struct RadixList {
   int r[kMaxStages];
 };
 
-#ifndef BSGP_FFT_COMPOSITE
-#define BSGP_FFT_COMPOSITE 1
-#endif
 // Stage radices of a static transform: 4s, then a 2 paired with a 3 as one
 // radix-6 stage, 3s paired as radix-9 stages, the rest, then 5s
 // (270 = 6*9*5: three LDS passes instead of five).
 // r8: radix-8 stages first (workgroup-wide transforms: 256 lanes, 2048 = 8*8*8*4).
-constexpr RadixList factor_radices(int n, bool comp = BSGP_FFT_COMPOSITE, bool r8 = false) {
+constexpr RadixList factor_radices(int n, bool comp = true, bool r8 = false) {
   RadixList L{0, {}};
   // one wave's 400- / 480-point transforms: three stages whose butterflies
   // fill the 64 lanes in 4 rounds in all (nb = 50, 40, 80 and 60, 80, 48)
@@ -453,7 +450,7 @@ BSGP_HD cd* stages_static(cd* in, cd* out, TW tw, bool inv, int lane, int nlanes
 // Transform of compile-time length N (must be 2/3/5-smooth).  COMP: composite
 // radix-6/9 stages (fewer LDS round trips, ~20 more VGPRs live in the stage);
 // R8: radix-8 stages first (for 256-lane workgroup transforms).
-template <int N, bool COMP = BSGP_FFT_COMPOSITE, bool R8 = false, class Sync, class TW>
+template <int N, bool COMP = true, bool R8 = false, class Sync, class TW>
 BSGP_HD cd* fft_run_static(cd* a, cd* b, TW tw, bool inv, int lane, int nlanes, Sync sync) {
   static_assert(factor_radices(N).n > 0, "N must be 2/3/5-smooth");
   return stages_static<N, 0, 1, COMP, R8>(a, b, tw, inv, lane, nlanes, sync);
@@ -488,19 +485,16 @@ BSGP_HD cd tw_step(const TwMixL& t, int m, bool inv) {
 
 // Workgroup-wide transform (all kBlock-style lanes, `sync` = workgroup
 // barrier): compile-time radix-8 plan for 2048 (config C4), runtime plan otherwise.
-#ifndef BSGP_COOP_TW2
-#define BSGP_COOP_TW2 1
-#endif
 // TW2 false: the global table even where the plan placed the LDS two-level
-// table (the column kernel's register budget, bsgp_device.hpp col_tw2).
+// table (the column passes' register budget, bsgp_device.hpp col_fft).
 template <bool TW2 = true, class Sync>
 BSGP_HD cd* fft_wide(cd* a, cd* b, const FftPlan& p, bool inv, int lane, int nlanes, Sync sync) {
   if (p.n == 2048) {
 #if defined(__HIP_DEVICE_COMPILE__)
     // the two-level table in LDS (bsgp_plan_create places it for every
-    // 2048-point plan when BSGP_COOP_TW2; load_tw_lds): a compile-time choice,
-    // so the kernels carry one 2048-point transform, not both
-    if constexpr (TW2 && BSGP_COOP_TW2) {
+    // cooperative 2048-point plan; load_tw_lds): a compile-time choice, so the
+    // kernels carry one 2048-point transform, not both
+    if constexpr (TW2) {
       const cd* t = reinterpret_cast<const cd*>(bsgp_dyn_lds + p.lds_tw2);
       return fft_run_static<2048, true, true>(a, b, Tw2{t, t + 64}, inv, lane, nlanes, sync);
     }
@@ -514,7 +508,7 @@ BSGP_HD cd* fft_wide(cd* a, cd* b, const FftPlan& p, bool inv, int lane, int nla
 // device every transform reads its twiddles from the LDS copy the kernel made
 // when the plan placed one (plan.lds_tw >= 0; LDS latency instead of L1/L2
 // latency in every butterfly round), else the global table.
-template <bool COMP = BSGP_FFT_COMPOSITE, class Sync>
+template <bool COMP = true, class Sync>
 BSGP_HD cd* fft_any(cd* a, cd* b, const FftPlan& p, bool inv, int lane, int nlanes, Sync sync) {
 #if defined(__HIP_DEVICE_COMPILE__)
   if (p.lds_tw >= 0) {

@@ -35,26 +35,11 @@ struct ImgState {
 
 // Everything a phase kernel needs (passed by value: kernel-argument loads are
 // scalar, so plan geometry and pointers stay in SGPRs).
-// Column passes run inside the phase kernels for one-workgroup images
-// instead of as k_col launches: A's at the end of k_dir (bit 0) or at the
-// start of k_ls (bit 2), AT's at the end of k_ls (bit 1).  Measured on C3
-// (A/B): AT's in k_ls +4.5 %; A's in k_dir -25 % (252 VGPRs + scratch: the
-// projection state stays live), A's also in k_ls -1 % (spills at 168 VGPRs).
-#ifndef BSGP_FUSE_COL
-#define BSGP_FUSE_COL 2
-#endif
-// teams of per-wave plans (C2): which column passes their row kernels run
-// after a team barrier instead of a k_col launch
-#ifndef BSGP_FUSE_COL_TEAM
-#define BSGP_FUSE_COL_TEAM 0
-#endif
-// fused-column code compiled into the kernels (a pass not compiled in costs no
-// registers in the kernels that never run it)
-#define BSGP_FUSE_COL_CODE (BSGP_FUSE_COL | BSGP_FUSE_COL_TEAM)
-// teams keep their projection lists in LDS when they fit (0: global, A/B)
-#ifndef BSGP_LIST_LDS
-#define BSGP_LIST_LDS 1
-#endif
+// One-workgroup images run AT's column pass at the end of k_ls instead of as
+// a k_col launch (SolveArgs::fuse_col; measured on C3, A/B: +4.5 %).  A's
+// column pass stays a k_col launch: fused into k_dir it cost 25 % (252 VGPRs +
+// scratch: the projection state stays live), at the start of k_ls 1 % (spills
+// at 168 VGPRs).  Teams launch k_col for both.
 
 // numpy float32 reduction program of a plan's N (bsgp_api.hip pairwise_program):
 // [nleaf][2] leaves (start, len), [nnode][2] node operands (value indices),
@@ -84,7 +69,7 @@ struct SolveArgs {
   // teams (T workgroups per image; T = 1: one workgroup, none of these used)
   int T;
   int Tc;               // workgroups per image of k_col (no reductions there: not a team)
-  int fuse_col;         // T == 1: BSGP_FUSE_COL (which phase kernels run the column passes)
+  int fuse_col;         // bit 1: AT's column pass runs at the end of k_ls (T == 1: 2, teams: 0)
   double* tpart;        // [B][kPartBufs][T][kMaxRed] reduction partials
   unsigned int* tctr;   // [B][kTeamWords] barrier words, then the timeout word; zeroed per solve
   int* tfail;           // set by a timed-out barrier spin
@@ -156,44 +141,10 @@ void persist_kernels_all(std::vector<const void*>& f);
 // Cooperative plans (Geo::coop) run the phase kernels of bsgp_solver_c512.hip:
 // the same kernels with 512-thread workgroups (two waves per SIMD per
 // workgroup where a long transform's LDS allows one or two workgroups per CU).
-// cooperative plans: at most this many thread groups per workgroup run
-// transforms side by side (bsgp_device.hpp coop passes), and the column
-// kernel's groups (0: the same as the other kernels)
-// plans whose per-wave transforms fit the LDS at three workgroups per CU (but
-// not four) take them instead of the cooperative build when this is <= 3
-// (runtime override: BSGP_PERWAVE_MIN_WG)
-#ifndef BSGP_PERWAVE_MIN_WG
-#define BSGP_PERWAVE_MIN_WG 2  // per-wave over cooperative (A/B): 375^2 tiles at 3 WG/CU, 1024 per
-                               // launch, 68.6 k -> 87.5 k image-it/s; 450^2 at 2 WG/CU 48.3 -> 59.7 k
-#endif
-#ifndef BSGP_PERWAVE_TW
-#define BSGP_PERWAVE_TW 1
-#endif
-#ifndef BSGP_COOP_GROUPS
-#define BSGP_COOP_GROUPS 4
-#endif
-#ifndef BSGP_POLL_LOOKAHEAD
-#define BSGP_POLL_LOOKAHEAD 1  // data-dependent stop rules: lookahead polling (bsgp_api.hip)
-#endif
-#ifndef BSGP_COOP_TW2
-#define BSGP_COOP_TW2 1  // two-level LDS twiddles for cooperative 2048-point transforms
-#endif
-#ifndef BSGP_SPEC_PAD
-#define BSGP_SPEC_PAD 0  // rows of padding per stored spectrum column (even)
-#endif
-#ifndef BSGP_VEC_PAD
-#define BSGP_VEC_PAD 0  // elements of padding after every per-image slot vector (multiple of 32)
-#endif
-#ifndef BSGP_COOP_ELEMS
-#define BSGP_COOP_ELEMS 8  // elements per thread a group may take when one batch leaves one group
-#endif
-#ifndef BSGP_COOP_COLGROUPS
-#define BSGP_COOP_COLGROUPS 0  // 375^2 tiles: k_col on 4 groups 1.49 -> 0.68 ms (A/B)
-#endif
-#ifndef BSGP_COOP512
-#define BSGP_COOP512 1
-#endif
-constexpr int kCoopBlock = BSGP_COOP512 ? 512 : kBlock;
+// At most this many thread groups per workgroup run a cooperative plan's
+// transforms side by side (bsgp_device.hpp coop passes).
+constexpr int kCoopGroups = 4;
+constexpr int kCoopBlock = 512;
 // threads per workgroup of a plan's phase kernels
 __host__ __device__ inline int plan_block(const Geo& g) { return g.coop ? kCoopBlock : kBlock; }
 // plans whose persistent solve runs the application-size build (bsgp_persist_app.hip):

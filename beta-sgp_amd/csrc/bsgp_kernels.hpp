@@ -24,23 +24,18 @@
 
 namespace bsgp {
 
-// The phase kernels are sized for 4 waves per SIMD (<= 128 VGPRs): four
-// 256-thread workgroups = four images per CU, so a 1024-image batch is
-// resident in one round on 256 CUs.
-#ifndef BSGP_OCC4
-#define BSGP_OCC4 __attribute__((amdgpu_waves_per_eu(4, 8)))
-#endif
+// Build configuration of a translation unit (defined before this header is
+// included; the defaults are the per-wave 256-thread builds'): BSGP_COL_ATTR,
+// BSGP_LS_ATTR, BSGP_PERSIST_ATTR (register budgets), BSGP_LS1_PRE / BSGP_BB_PRE
+// and the *_PIPE switches (operand batching of the single-column row passes,
+// bsgp_persist_app.hip), BSGP_LS1_K2, BSGP_ACC_SERIES.  Everything else below
+// is a constant: the value each A/B settled on, with its measurement.
 
-// Operand batching of the inverse row passes (tuning knobs, see row_inv2)
+// Operand batching of the inverse row passes (see row_inv2)
 #ifndef BSGP_LS1_PRE
 #define BSGP_LS1_PRE false
 #endif
-#ifndef BSGP_LS1_JCH
-#define BSGP_LS1_JCH 1
-#endif
-#ifndef BSGP_DIR_ATTR
-#define BSGP_DIR_ATTR
-#endif
+constexpr int kLs1Jch = 1;
 #ifndef BSGP_COL_ATTR
 #define BSGP_COL_ATTR
 #endif
@@ -51,32 +46,30 @@ namespace bsgp {
 #ifndef BSGP_LS_ATTR
 #define BSGP_LS_ATTR __attribute__((amdgpu_waves_per_eu(COOP ? 1 : ((K <= 2 && !ADAPT) ? 3 : 2))))
 #endif
-// line search: pass 1 also sums the second trial (lam = beta) directly.  On in
-// the per-wave float64 builds (bsgp_persist.hip and bsgp_solver.hip's phase
-// kernels, which must stay bitwise equal to it; A/B same box: C3 +0.5 %,
-// 1.41 -> 1.21 passes per iteration, C5 -0.1 %); never in the cooperative
-// kernels, whose k_ls spills with it (C4 -3.7 %).
+// line search: pass 1 also sums the second trial (lam = beta) directly (A/B
+// same box: C3 +0.5 %, 1.41 -> 1.21 passes per iteration, C5 -0.1 %).  Two
+// translation units turn it on, bsgp_solver.hip and bsgp_persist.hip: the
+// per-wave float64 phase kernels and the per-wave float64 persistent solver,
+// which must stay bitwise equal to each other.  Every other unit leaves it at
+// this 0 on purpose: bsgp_persist_app.hip, the float32 units
+// (bsgp_solver_f32.hip, bsgp_persist_f32.hip) and the three 512-thread
+// cooperative units, whose k_ls spills with it (C4 -3.7 %; the code is
+// compiled out of COOP kernels in any case).  A different trial sum is a
+// different rounding, so the builds with and without it are not bitwise equal.
 #ifndef BSGP_LS1_K2
 #define BSGP_LS1_K2 0
 #endif
-// closed-form line-search trials evaluated kLsLanes at a time, one per lane
-// (ls_phase); 0 = one trial per step (the scalar loop, A/B)
-#ifndef BSGP_LS_SERIES_LANES
-#define BSGP_LS_SERIES_LANES 1
-#endif
+// closed-form line-search trials are evaluated kLsLanes at a time, one per
+// lane (ls_phase)
 constexpr int kLsLanes = 32;
-#ifndef BSGP_SERIES_BOUND
-#define BSGP_SERIES_BOUND 1  // closed-form trials past lam*max|u| <= 0.01 under the tail bound
-#endif
+// den^(b-1) by the series at series-step accepts: same speed on C3 (A/B), off.
+// Kept as a switch: deleting its code changes one instruction of the
+// application-size persistent build (bsgp_persist_app.hip: a commuted add).
 #ifndef BSGP_ACC_SERIES
-#define BSGP_ACC_SERIES 0  // den^(b-1) by the series at series-step accepts: same speed on C3 (A/B), off
+#define BSGP_ACC_SERIES 0
 #endif
-#ifndef BSGP_LSACC_JCH
-#define BSGP_LSACC_JCH 1
-#endif
-#ifndef BSGP_LSACC_PF
-#define BSGP_LSACC_PF true
-#endif
+constexpr int kLsAccJch = 1;
+constexpr bool kLsAccPf = true;
 // two operand batches in flight in the single-column row passes (row_inv2 /
 // row_fwd2 PIPE): k_ls pass 1 and accept, k_bb
 #ifndef BSGP_LS1_PIPE
@@ -88,32 +81,18 @@ constexpr int kLsLanes = 32;
 #ifndef BSGP_BB_PIPE
 #define BSGP_BB_PIPE false
 #endif
-#ifndef BSGP_PROJ_U
-#define BSGP_PROJ_U 4
-#endif
-#ifndef BSGP_DIR_JCH
-#define BSGP_DIR_JCH 4
-#endif
-#ifndef BSGP_DIR_PF
-#define BSGP_DIR_PF true
-#endif
+constexpr int kProjU = 4;  // pixel pairs in flight per thread in the projection's passes
+constexpr int kDirJch = 4;
+constexpr bool kDirPf = true;
 // composite radix-6/9 FFT stages per row pass (the column pass always uses them):
 // fewer LDS round trips vs ~20 more live VGPRs
-#ifndef BSGP_DIR_COMP
-#define BSGP_DIR_COMP true
-#endif
-#ifndef BSGP_LS_COMP
-#define BSGP_LS_COMP false
-#endif
-#ifndef BSGP_BB_COMP
-#define BSGP_BB_COMP false
-#endif
+constexpr bool kDirComp = true;
+constexpr bool kLsComp = false;
+constexpr bool kBbComp = false;
 #ifndef BSGP_BB_PRE
 #define BSGP_BB_PRE false
 #endif
-#ifndef BSGP_BB_JCH
-#define BSGP_BB_JCH 1  // one column per operand batch: 117 VGPRs, 4 waves/SIMD (k_bb -17 %, A/B)
-#endif
+constexpr int kBbJch = 1;  // one column per operand batch: 117 VGPRs, 4 waves/SIMD (k_bb -17 %, A/B)
 
 // (phase profile macros PH_T / PH_ADD: bsgp_device.hpp)
 // ------------------------------------------------------------------ helpers
@@ -312,7 +291,7 @@ __device__ __forceinline__ Team make_team(const SolveArgs& A, int img, const Img
   t.T = A.T;
   t.m = A.T == 1 ? 0 : (int)(blockIdx.x % (unsigned)A.T);
   t.part = A.tpart ? A.tpart + (size_t)img * kPartBufs * (A.T + 8) * kMaxRed : nullptr;
-  t.flags = A.T <= 1 ? 0 : A.T <= BSGP_TEAM_FLAGS ? 1 : (BSGP_TEAM_HIER && A.T >= 8) ? 2 : 0;
+  t.flags = A.T <= 1 ? 0 : A.T <= kTeamFlags ? 1 : A.T >= 8 ? 2 : 0;
   t.ctr = A.tctr ? A.tctr + (size_t)img * kTeamWords : nullptr;
   t.base = (unsigned int)st.bar_base;
   t.nb = 0;
@@ -431,17 +410,6 @@ __device__ __forceinline__ void count_stopped(const SolveArgs& A) {
 // ------------------------------------------------------------ kernel: setup
 // sgp.py:163-298 (= 617-742): scaling, null pixels, flux, x0, initial
 // projection, x_tf = A(x), f, g and the scaling-matrix bounds.
-// Waves per SIMD the setup kernel is compiled for (per-wave plans; 0: the
-// compiler's choice).  Setup runs once per solve, one workgroup per image:
-// at four workgroups per CU C3's 1024 images are one round instead of two.
-#ifndef BSGP_SETUP_WAVES
-#define BSGP_SETUP_WAVES 0
-#endif
-#if BSGP_SETUP_WAVES
-#define BSGP_SETUP_ATTR __attribute__((amdgpu_waves_per_eu(COOP ? 1 : BSGP_SETUP_WAVES)))
-#else
-#define BSGP_SETUP_ATTR
-#endif
 // One image's setup (k_setup below, or the persistent solver's first task of
 // the image, SolveArgs::fold_setup); the caller has loaded the twiddles into LDS.
 template <bool COOP, class V>
@@ -702,7 +670,7 @@ __device__ __forceinline__ void setup_phase(const SolveArgs& A, int img) {
 }
 
 template <bool COOP, class V>
-__global__ void __launch_bounds__(kBlock) BSGP_SETUP_ATTR k_setup(SolveArgs A) {
+__global__ void __launch_bounds__(kBlock) k_setup(SolveArgs A) {
   load_tw_lds(A.g);
   setup_phase<COOP, V>(A, team_img(A));
 }
@@ -726,10 +694,7 @@ __global__ void __launch_bounds__(kBlock) BSGP_SETUP_ATTR k_setup(SolveArgs A) {
 // bound (for the convex sum the secant and Newton iterates fall on either
 // side of the root); on later misses, the tightest bracket of signs seen.
 // A miss is just a full pass, so the choice of bracket never changes results.
-#ifndef BSGP_PROJ_GUESS_W
-#define BSGP_PROJ_GUESS_W 0.3
-#endif
-constexpr double kProjGuessW = BSGP_PROJ_GUESS_W;
+constexpr double kProjGuessW = 0.3;
 // Round 6: the first pass's bracket from the search's own history.  The root
 // moves with the step length alpha of y = x - alpha X g (without clipping,
 // sum x = flux makes lambda = alpha sum(X g) / sum X): C3's stagnating
@@ -742,15 +707,8 @@ constexpr double kProjGuessW = BSGP_PROJ_GUESS_W;
 // multiplier sequences (oracle) through these rules: full passes + list
 // reads per projection 1.97 -> 1.33 pass-equivalents on C3's images 0-1,
 // 2.39 -> 1.80 on C4.  A miss is still just a full pass: results unchanged.
-#ifndef BSGP_PROJ_ALPHA
-#define BSGP_PROJ_ALPHA 1
-#endif
-#ifndef BSGP_PROJ_W1
-#define BSGP_PROJ_W1 0.1
-#endif
-#ifndef BSGP_PROJ_W2
-#define BSGP_PROJ_W2 0.2
-#endif
+constexpr double kProjW1 = 0.1;
+constexpr double kProjW2 = 0.2;
 // Teams with few pixels per thread (C2: 8) split the first pass for
 // [lambda_ - dlambda_, lambda_ + dlambda_] instead: the reference's bracketing
 // phase stops there whenever r(0) and r(-/+1) differ in sign (every iteration
@@ -758,9 +716,7 @@ constexpr double kProjGuessW = BSGP_PROJ_GUESS_W;
 // bracket, so no evaluation misses; the wider list costs a few entries per
 // thread where each evaluation is one team reduction either way.  (The root
 // moves 2-25x between iterations there, so the +/-30 % guess missed on most.)
-#ifndef BSGP_PROJ_WIDE_PX
-#define BSGP_PROJ_WIDE_PX 16
-#endif
+constexpr int kProjWidePx = 16;
 
 // Teams keep the first SolveArgs::list_lds entries of every thread's list in
 // the transform buffers' LDS, which the row pass after the projection is the
@@ -848,7 +804,7 @@ __device__ __forceinline__ ProjOut cached_projection(const SolveArgs& A, int img
         }
       }
     };
-    stream2<BSGP_PROJ_U>(
+    stream2<kProjU>(
         Pt, npair,
         [&](int p) {
           struct Ld {
@@ -910,18 +866,18 @@ __device__ __forceinline__ ProjOut cached_projection(const SolveArgs& A, int img
     if (calls == 0) {
       const double lams[3] = {lam, lam - 1.0, lam + 1.0};  // lambda_ -/+ dlambda_ (dlambda_ = 1)
       double Sv[3];
-      const bool wide = tm.T > 1 && (long)N <= (long)BSGP_PROJ_WIDE_PX * LS;
+      const bool wide = tm.T > 1 && (long)N <= (long)kProjWidePx * LS;
       bool guess = wide || (isfinite(lam_prev) && lam_prev != 0.0);
       const double w = kProjGuessW * fabs(lam_prev);
       double gL = wide ? lams[1] : lam_prev - w, gU = wide ? lams[2] : lam_prev + w;
       const double lh = D.alpha * lam_ratio;
-      if (BSGP_PROJ_ALPHA && !wide && isfinite(lh) && lh != 0.0) {
-        gL = lh - BSGP_PROJ_W1 * fabs(lh);
-        gU = lh + BSGP_PROJ_W1 * fabs(lh);
+      if (!wide && isfinite(lh) && lh != 0.0) {
+        gL = lh - kProjW1 * fabs(lh);
+        gU = lh + kProjW1 * fabs(lh);
         const double pk = kappa * lh;
         if (isfinite(pk) && pk != 0.0) {
-          gL = fmin(gL, pk - BSGP_PROJ_W2 * fabs(pk));
-          gU = fmax(gU, pk + BSGP_PROJ_W2 * fabs(pk));
+          gL = fmin(gL, pk - kProjW2 * fabs(pk));
+          gU = fmax(gU, pk + kProjW2 * fabs(pk));
         }
         guess = true;
       }
@@ -1039,7 +995,7 @@ __device__ __forceinline__ void dir_phase(const SolveArgs& A, int img) {
   PH_ADD(0, tk0);
   PH_T(tk1);
   double gd[1] = {0.0};
-  row_fwd2<BSGP_DIR_JCH, BSGP_DIR_PF, BSGP_DIR_COMP, COOP, false, 22>(
+  row_fwd2<kDirJch, kDirPf, kDirComp, COOP, false, 22>(
       G, Pt, G.H, G.W, G.sld, B.spec, lds,
       [&](int r, int j) {
         const int i = r * G.W + j;
@@ -1052,12 +1008,6 @@ __device__ __forceinline__ void dir_phase(const SolveArgs& A, int img) {
       });
   team_sum<1>(gd, red, tm);
   PH_ADD(1, tk1);
-  if ((BSGP_FUSE_COL_CODE & 1) && (A.fuse_col & 1)) {  // A's column pass follows here
-    PH_T(tc0);
-    team_sync(tm);
-    col_conv<COOP>(G, Pt, B.spec, tf_of(G, img, 0), lds);
-    PH_ADD(3, tc0);
-  }
   PH_ADD(2, tk0);
   team_end(st, tm);
   if (leader(tm)) {  // sgp.py:306-308 (memory shifts) + direction scalars
@@ -1076,7 +1026,7 @@ __device__ __forceinline__ void dir_phase(const SolveArgs& A, int img) {
 }
 
 template <bool COOP, class V>
-__global__ void __launch_bounds__(kBlock) BSGP_DIR_ATTR k_dir(SolveArgs A) {
+__global__ void __launch_bounds__(kBlock) k_dir(SolveArgs A) {
   const int img = team_img(A);
   if (A.st[img].stop) return;
   load_tw_lds(A.g);
@@ -1127,12 +1077,6 @@ __device__ __forceinline__ void ls_phase(const SolveArgs& A, int img) {
   const double lr_st = st.lr;
   constexpr bool adapt = ADAPT;  // adaptive beta (sgp.py:798-800): K == 1, runtime mode
   Bufs<V> B = slot_bufs<V>(A, img, st.par);
-  if ((BSGP_FUSE_COL_CODE & 4) && (A.fuse_col & 4)) {  // A's column pass of k_dir's rows
-    PH_T(tc0);
-    col_conv<COOP>(G, Pt, B.spec, tf_of(G, img, 0), lds);
-    team_sync(tm);
-    PH_ADD(3, tc0);
-  }
   const double bks_scalar = st.bks_scalar;
   const double flux = st.flux;
   const double gd = st.gd;
@@ -1211,7 +1155,7 @@ __device__ __forceinline__ void ls_phase(const SolveArgs& A, int img) {
   // <= 0.004) it covers every trial after the first, where lam * max|u| <=
   // kSeriesRho left lam = 0.4 to a direct pass (0.46 passes per iteration).
   constexpr double kSeriesTail = 8.673617379884035e-19;  // 2^-60
-  const bool tail_bound = BSGP_SERIES_BOUND && obj.beta >= 0.0 && obj.beta <= MS + 2;
+  const bool tail_bound = obj.beta >= 0.0 && obj.beta <= MS + 2;
   const bool series = (MODE == 3 || MODE == 4) && !adapt && P.ls_series != 0;
   // the moments and binomial coefficients are the same in every thread: they
   // live in LDS after the first pass (ser[0..3][MS+1] = P, Q, binom(b, m),
@@ -1239,7 +1183,7 @@ __device__ __forceinline__ void ls_phase(const SolveArgs& A, int img) {
     struct LsIn {
       double x0, g, p0, bkv;
     };
-    row_inv2<BSGP_LS1_PRE, BSGP_LS1_JCH, BSGP_LS_COMP, COOP, BSGP_LS1_PIPE, 13>(
+    row_inv2<BSGP_LS1_PRE, kLs1Jch, kLsComp, COOP, BSGP_LS1_PIPE, 13>(
         G, Pt, B.spec, lds,
         [&](int r, int j) {
           const int i = r * G.W + j;
@@ -1371,14 +1315,14 @@ __device__ __forceinline__ void ls_phase(const SolveArgs& A, int img) {
       continue;
     }
     have2 = false;
-    if (BSGP_LS_SERIES_LANES && series && series_ok(lam)) {
-      // Closed-form trials, kLsLanes at once: lane j of every wave evaluates
-      // the j-th next trial, lam * beta^j (the same sequential products the
-      // one-trial-at-a-time loop below forms, so the same bits), with the same
-      // arithmetic as that loop.  The first lane whose trial ends the search
-      // decides: it accepts, it is past the closed form's range (a direct pass
-      // from there on), or it fails at the trial cap.  Every wave computes the
-      // same decision (scalar control stays identical in every thread).
+    if (series && series_ok(lam)) {
+      // Closed-form trials (no pass over the image), kLsLanes at once: lane j
+      // of every wave evaluates the j-th next trial, lam * beta^j (the
+      // sequential products of a one-trial-at-a-time loop, so the same bits).
+      // The first lane whose trial ends the search decides: it accepts, it is
+      // past the closed form's range (a direct pass from there on), or it
+      // fails at the trial cap.  Every wave computes the same decision (scalar
+      // control stays identical in every thread).
       constexpr int L = kLsLanes;
       const int ln = (int)(threadIdx.x & 63u);
       const int lj = ln < L ? ln : L - 1;
@@ -1417,31 +1361,6 @@ __device__ __forceinline__ void ls_phase(const SolveArgs& A, int img) {
         break;
       }
       lam = lt_j * P.beta;
-      if (nls > ls_cap) {
-        status = 1;
-        break;
-      }
-      continue;
-    }
-    if (series && series_ok(lam)) {
-      // closed-form trial: no pass over the image
-      double s0 = 0.0, s1 = 0.0, lm = 1.0;
-      for (int m = 0; m <= MS; ++m) {
-        s0 += ser[2 * (MS + 1) + m] * lm * ser[m];
-        s1 += ser[3 * (MS + 1) + m] * lm * ser[MS + 1 + m];
-        lm *= lam;
-      }
-      const double fk =
-          obj.combine(konst, obj.c1 * s0, (MODE == 4 ? 1.0 : obj.c2) * s1, flux, (double)N);
-      ++nls;
-      ++series_evals;
-      if (fk <= fr + P.gamma * lam * gd || lam < 1e-12) {
-        f_acc = fk;
-        accepted = true;
-        acc_series = true;
-        break;
-      }
-      lam = lam * P.beta;
       if (nls > ls_cap) {
         status = 1;
         break;
@@ -1534,7 +1453,7 @@ __device__ __forceinline__ void ls_phase(const SolveArgs& A, int img) {
   struct AcIn {
     double x, d, g, bkv, p0;
   };
-  row_fwd2<BSGP_LSACC_JCH, BSGP_LSACC_PF, BSGP_LS_COMP, COOP, BSGP_LSACC_PIPE, 16>(
+  row_fwd2<kLsAccJch, kLsAccPf, kLsComp, COOP, BSGP_LSACC_PIPE, 16>(
       G, Pt, G.H, G.W, G.sld, B.spec, lds,
       [&](int r, int j) {
         const int i = r * G.W + j;
@@ -1568,7 +1487,7 @@ __device__ __forceinline__ void ls_phase(const SolveArgs& A, int img) {
         return g * (p / den);
       });
   PH_ADD(6, tk2);
-  if ((BSGP_FUSE_COL_CODE & 2) && (A.fuse_col & 2)) {  // AT's column pass follows here
+  if (A.fuse_col & 2) {  // AT's column pass follows here
     PH_T(tc0);
     team_sync(tm);
     col_conv<COOP>(G, Pt, B.spec, tf_of(G, img, 1), lds);
@@ -1636,7 +1555,7 @@ __device__ __forceinline__ void bb_phase(const SolveArgs& A, int img) {
   struct BbIn {
     double p, x, g;
   };
-  row_inv2<BSGP_BB_PRE, BSGP_BB_JCH, BSGP_BB_COMP, COOP, BSGP_BB_PIPE, 19>(
+  row_inv2<BSGP_BB_PRE, kBbJch, kBbComp, COOP, BSGP_BB_PIPE, 19>(
       G, Pt, B.spec, lds,
       [&](int r, int j) {
         const int i = r * G.W + j;
@@ -1793,15 +1712,8 @@ static __global__ void k_ring_init(unsigned* queue, int nimg, int img0) {
 
 #ifndef BSGP_PERSIST_ATTR
 // (per-wave plans: 3 waves/SIMD, the phase kernels' own; cooperative plans'
-// 512-thread workgroups: 2 waves/SIMD per workgroup, BSGP_PERSIST_COOP_WAVES)
-#ifndef BSGP_PERSIST_COOP_WAVES
-#define BSGP_PERSIST_COOP_WAVES 2
-#endif
-#ifndef BSGP_PERSIST_WAVES
-#define BSGP_PERSIST_WAVES 3
-#endif
-#define BSGP_PERSIST_ATTR \
-  __attribute__((amdgpu_waves_per_eu(COOP ? BSGP_PERSIST_COOP_WAVES : BSGP_PERSIST_WAVES)))
+// 512-thread workgroups: 2 waves/SIMD per workgroup)
+#define BSGP_PERSIST_ATTR __attribute__((amdgpu_waves_per_eu(COOP ? 2 : 3)))
 #endif
 
 __device__ __forceinline__ unsigned long long ld_sc1_u64(const unsigned long long* p) {
@@ -1818,17 +1730,6 @@ __device__ __forceinline__ unsigned long long ld_sc1_u64(const unsigned long lon
 // scalar state of all phases at once); as calls the only spill code is each
 // phase's callee-saved registers at its entry and exit (~210 VGPRs per wave
 // per task, ~3 % of a task's bytes, L2-resident).
-#ifndef BSGP_PERSIST_SB
-#define BSGP_PERSIST_SB 1
-#endif
-#ifndef BSGP_PERSIST_CALLS
-#define BSGP_PERSIST_CALLS 1
-#endif
-#if BSGP_PERSIST_CALLS
-#define BSGP_PERSIST_FN __attribute__((noinline))
-#else
-#define BSGP_PERSIST_FN __forceinline__
-#endif
 struct ArgRef {
   unsigned lo, hi;  // address of the kernel's SolveArgs (kernarg segment)
 };
@@ -1847,15 +1748,15 @@ __device__ __forceinline__ const SolveArgs& args_of(ArgRef r) {
   return *(const SolveArgs*)p;
 }
 template <bool COOP, class V>
-__device__ BSGP_PERSIST_FN void persist_setup(ArgRef r, int img) {
+__device__ __attribute__((noinline)) void persist_setup(ArgRef r, int img) {
   setup_phase<COOP, V>(args_of(r), __builtin_amdgcn_readfirstlane(img));
 }
 template <bool COOP, class V>
-__device__ BSGP_PERSIST_FN void persist_dir(ArgRef r, int img) {
+__device__ __attribute__((noinline)) void persist_dir(ArgRef r, int img) {
   dir_phase<COOP, V, false>(args_of(r), __builtin_amdgcn_readfirstlane(img));
 }
 template <bool COOP>
-__device__ BSGP_PERSIST_FN void persist_col_a(ArgRef r, int img) {
+__device__ __attribute__((noinline)) void persist_col_a(ArgRef r, int img) {
   const SolveArgs& A = args_of(r);
   img = __builtin_amdgcn_readfirstlane(img);
   BSGP_LDS_VIEWS(A);
@@ -1870,11 +1771,11 @@ __device__ BSGP_PERSIST_FN void persist_col_a(ArgRef r, int img) {
   PH_ADD(3, tc0);
 }
 template <int K, int MODE, bool ADAPT, bool COOP, class V, bool SB = false>
-__device__ BSGP_PERSIST_FN void persist_ls(ArgRef r, int img) {
+__device__ __attribute__((noinline)) void persist_ls(ArgRef r, int img) {
   ls_phase<K, MODE, ADAPT, COOP, V, SB>(args_of(r), __builtin_amdgcn_readfirstlane(img));
 }
 template <bool COOP, class V>
-__device__ BSGP_PERSIST_FN void persist_bb(ArgRef r, int img) {
+__device__ __attribute__((noinline)) void persist_bb(ArgRef r, int img) {
   bb_phase<COOP, V>(args_of(r), __builtin_amdgcn_readfirstlane(img));
 }
 
@@ -2049,13 +1950,25 @@ __global__ void __launch_bounds__(kBlock) k_persist_finalize(SolveArgs A) {
   }
 }
 
+// Objective mode of a solve's line-search code (the MODE of k_ls / k_persist):
+// 0 KL, -1 the special betas 0 and 1 (runtime mode), 3 general beta, 4 general
+// beta on a float32 image; *adapt: adaptive beta (K = 1, runtime mode).  The
+// one derivation: the host sizes the grid from the occupancy of the kernel it
+// then launches.
+inline int ls_mode(const SolveArgs& a, bool* adapt) {
+  const bsgp_params& P = a.prm;
+  *adapt = P.adapt_beta && P.variant == BSGP_VARIANT_BETA;
+  const bool special = a.in.beta0 ? !P.beta0_general : (P.betaParam == 0.0 || P.betaParam == 1.0);
+  return P.variant == BSGP_VARIANT_KL ? 0 : special ? -1 : P.gn_f32 ? 4 : 3;
+}
+
 // The persistent kernel for a trial width / objective mode (the same choice as
-// ls_kernel); nullptr where no persistent build exists (the phase kernels run).
+// ls_kernel).
 template <class V, bool COOP = false>
 inline const void* persist_kernel(int K, int mode, bool adapt, bool scalar_bkg = false) {
   // the timed workload's combination (general beta, trial width 2, scalar
   // backgrounds) has a build without the per-pixel background operand
-  if (!COOP && BSGP_PERSIST_SB && scalar_bkg && !adapt && mode == 3 && K >= 2)
+  if (!COOP && scalar_bkg && !adapt && mode == 3 && K >= 2)
     return (const void*)k_persist<COOP, 2, 3, false, V, true>;
   if (adapt) return (const void*)k_persist<COOP, 1, -1, true, V>;
   if (K > 2) K = 2;
@@ -2072,7 +1985,7 @@ inline void persist_kernels(std::vector<const void*>& f) {
   for (int adapt = 0; adapt < 2; ++adapt)
     for (int mode : {-1, 0, 3, 4})
       for (int K : {1, 2}) f.push_back(persist_kernel<V, COOP>(K, mode, adapt != 0));
-  if (!COOP && BSGP_PERSIST_SB) f.push_back(persist_kernel<V, COOP>(2, 3, false, true));
+  if (!COOP) f.push_back(persist_kernel<V, COOP>(2, 3, false, true));
 }
 template <class V, bool COOP = false>
 inline hipError_t launch_persist_t(const SolveArgs& a, int K, size_t lds, hipStream_t s,
@@ -2080,10 +1993,8 @@ inline hipError_t launch_persist_t(const SolveArgs& a, int K, size_t lds, hipStr
   if (a.prm.stop_criterion >= 2 && a.prm.stop_criterion <= 4)
     hipLaunchKernelGGL(k_ring_init, dim3((a.nimg + 255) / 256), dim3(256), 0, s, queue, a.nimg,
                        a.img0);
-  const bsgp_params& P = a.prm;
-  const bool adapt = P.adapt_beta && P.variant == BSGP_VARIANT_BETA;
-  const bool special = a.in.beta0 ? !P.beta0_general : (P.betaParam == 0.0 || P.betaParam == 1.0);
-  const int mode = P.variant == BSGP_VARIANT_KL ? 0 : special ? -1 : P.gn_f32 ? 4 : 3;
+  bool adapt = false;
+  const int mode = ls_mode(a, &adapt);
   SolveArgs aa = a;
   void* args[] = {&aa, &queue, &done};
   hipError_t e = hipLaunchKernel(persist_kernel<V, COOP>(K, mode, adapt, !a.prm.bkg_is_map), dim3(grid),
@@ -2158,16 +2069,11 @@ inline const void* ls_kernel(int K, int mode, bool adapt) {
 // teams from the occupancy the runtime reports for every team kernel of the
 // plan's build (team_resident_per_cu), so the grid fits the idle device; the
 // barrier's bounded spin turns a violation (another tenant holding CUs) into
-// status bit 4 instead of a hang.  BSGP_COOP_LAUNCH=1 launches them
-// cooperatively instead, which the runtime guarantees but which costs ~17 us
-// per launch (C2 -29 %, C4 -6 %, measured A/B).
-#ifndef BSGP_COOP_LAUNCH
-#define BSGP_COOP_LAUNCH 0
-#endif
+// status bit 4 instead of a hang.  (hipLaunchCooperativeKernel would
+// guarantee it, but costs ~17 us per launch: C2 -29 %, C4 -6 %, measured A/B
+// and removed.)
 inline hipError_t launch_fn(const void* f, dim3 grid, size_t lds, hipStream_t s, const SolveArgs& a) {
   void* args[] = {const_cast<SolveArgs*>(&a)};
-  if (BSGP_COOP_LAUNCH && a.T > 1)
-    return hipLaunchCooperativeKernel(f, grid, dim3(kBlock), args, (unsigned)lds, s);
   return hipLaunchKernel(f, grid, dim3(kBlock), args, lds, s);
 }
 // k_col (no barrier: a team image's columns are independent)
@@ -2196,18 +2102,12 @@ inline hipError_t launch_iteration_t(const SolveArgs& a, int K, size_t lds, hipS
   if (ev) chk(hipEventRecord(ev[1], s));
   // k_col of a cooperative plan needs only its own groups' buffers (no
   // reduction scratch, no LDS twiddles)
-#ifndef BSGP_COL_LDS_FULL
-#define BSGP_COL_LDS_FULL 0
-#endif
-  const size_t lds_col =
-      (COOP && !BSGP_COL_LDS_FULL) ? (size_t)a.g.nfc * 2 * a.g.lpad * sizeof(cd) + a.g.tw2 : lds;
-  if (!(a.fuse_col & 5)) chk(launch_fn((const void*)k_col<COOP>, gcol, lds_col, s, a, 0));
+  const size_t lds_col = COOP ? (size_t)a.g.nfc * 2 * a.g.lpad * sizeof(cd) + a.g.tw2 : lds;
+  chk(launch_fn((const void*)k_col<COOP>, gcol, lds_col, s, a, 0));
   if (ev) chk(hipEventRecord(ev[2], s));
   // line-search kernel specialised on trial width, objective mode, adaptivity
-  const bsgp_params& P = a.prm;
-  const bool adapt = P.adapt_beta && P.variant == BSGP_VARIANT_BETA;
-  const bool special = a.in.beta0 ? !P.beta0_general : (P.betaParam == 0.0 || P.betaParam == 1.0);
-  const int mode = P.variant == BSGP_VARIANT_KL ? 0 : special ? -1 : P.gn_f32 ? 4 : 3;
+  bool adapt = false;
+  const int mode = ls_mode(a, &adapt);
   chk(launch_fn(ls_kernel<COOP, V>(K, mode, adapt), grid, lds, s, a));
   if (ev) chk(hipEventRecord(ev[3], s));
   if (!(a.fuse_col & 2)) chk(launch_fn((const void*)k_col<COOP>, gcol, lds_col, s, a, 1));
@@ -2244,13 +2144,12 @@ inline hipError_t team_resident(const std::vector<const void*>& fns, size_t lds,
   *per_cu = m;
   return hipSuccess;
 }
-hipError_t team_resident_per_cu(bool coop, int storage, size_t lds, int* per_cu);
 
 // float32-storage builds (bsgp_solver_f32.hip)
 hipError_t launch_setup_f32(const SolveArgs& a, size_t lds, hipStream_t s);
 hipError_t launch_iteration_f32(const SolveArgs& a, int K, size_t lds, hipStream_t s,
                                 hipEvent_t* ev);
 hipError_t launch_track_f32(const SolveArgs& a, int it, hipStream_t s);
-void solver_kernels_f32(std::vector<const void*>& f, bool coop);
+void solver_kernels_f32(std::vector<const void*>& f);
 
 }  // namespace bsgp

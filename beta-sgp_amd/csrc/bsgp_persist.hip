@@ -9,8 +9,11 @@
 
 #include <vector>
 
+// pass 1 of the line search also sums the second trial, as in the per-wave
+// float64 phase kernels (bsgp_solver.hip): the two stay bitwise equal
+// (bsgp_kernels.hpp; the float32 and application-size builds leave it off)
 #ifndef BSGP_LS1_K2
-#define BSGP_LS1_K2 1  // (bsgp_kernels.hpp)
+#define BSGP_LS1_K2 1
 #endif
 #include "bsgp_kernels.hpp"
 
@@ -20,13 +23,6 @@ hipError_t launch_persist_f32(const SolveArgs& a, int K, size_t lds, hipStream_t
                               unsigned* queue, unsigned* done, int grid);
 const void* persist_kernel_f32(int K, int mode, bool adapt, bool scalar_bkg);
 void persist_kernels_f32(std::vector<const void*>& f);
-
-static int persist_mode(const SolveArgs& a, bool* adapt) {
-  const bsgp_params& P = a.prm;
-  *adapt = P.adapt_beta && P.variant == BSGP_VARIANT_BETA;
-  const bool special = a.in.beta0 ? !P.beta0_general : (P.betaParam == 0.0 || P.betaParam == 1.0);
-  return P.variant == BSGP_VARIANT_KL ? 0 : special ? -1 : P.gn_f32 ? 4 : 3;
-}
 
 hipError_t launch_persist(const SolveArgs& a, int K, size_t lds, hipStream_t s, unsigned* queue,
                           unsigned* done, int grid) {
@@ -42,7 +38,7 @@ hipError_t persist_resident_per_cu(const SolveArgs& a, int K, size_t lds, int* p
   if (a.g.coop) return bsgp_c512_persist_resident(&a, K, lds, per_cu);
   if (app_static_plan(a.g, a.storage)) return bsgp_app_persist_resident(&a, K, lds, per_cu);
   bool adapt = false;
-  const int mode = persist_mode(a, &adapt);
+  const int mode = ls_mode(a, &adapt);
   const bool sb = !a.prm.bkg_is_map;
   const void* f = a.storage == BSGP_STORAGE_F32 ? persist_kernel_f32(K, mode, adapt, sb)
                                                 : persist_kernel<double>(K, mode, adapt, sb);

@@ -33,17 +33,6 @@
 #define bsgp bsgp_app
 #include "bsgp_kernels.hpp"
 
-namespace bsgp {
-
-static int persist_mode_app(const SolveArgs& a, bool* adapt) {
-  const bsgp_params& P = a.prm;
-  *adapt = P.adapt_beta && P.variant == BSGP_VARIANT_BETA;
-  const bool special = a.in.beta0 ? !P.beta0_general : (P.betaParam == 0.0 || P.betaParam == 1.0);
-  return P.variant == BSGP_VARIANT_KL ? 0 : special ? -1 : P.gn_f32 ? 4 : 3;
-}
-
-}  // namespace bsgp
-
 extern "C" {
 
 size_t bsgp_app_args_size(void) { return sizeof(bsgp_app::SolveArgs); }
@@ -57,7 +46,7 @@ hipError_t bsgp_app_launch_persist(const void* a, int K, size_t lds, hipStream_t
 hipError_t bsgp_app_persist_resident(const void* a, int K, size_t lds, int* per_cu) {
   const bsgp_app::SolveArgs& A = *static_cast<const bsgp_app::SolveArgs*>(a);
   bool adapt = false;
-  const int mode = bsgp_app::persist_mode_app(A, &adapt);
+  const int mode = bsgp_app::ls_mode(A, &adapt);
   return hipOccupancyMaxActiveBlocksPerMultiprocessor(
       per_cu, bsgp_app::persist_kernel<double>(K, mode, adapt, !A.prm.bkg_is_map),
       bsgp_app::kBlock, lds);

@@ -26,13 +26,6 @@ hipError_t launch_persist_coop_f32(const SolveArgs& a, int K, size_t lds, hipStr
 const void* persist_kernel_coop_f32(int K, int mode, bool adapt);
 void persist_kernels_coop_f32(std::vector<const void*>& f);
 
-static int persist_mode_coop(const SolveArgs& a, bool* adapt) {
-  const bsgp_params& P = a.prm;
-  *adapt = P.adapt_beta && P.variant == BSGP_VARIANT_BETA;
-  const bool special = a.in.beta0 ? !P.beta0_general : (P.betaParam == 0.0 || P.betaParam == 1.0);
-  return P.variant == BSGP_VARIANT_KL ? 0 : special ? -1 : P.gn_f32 ? 4 : 3;
-}
-
 }  // namespace bsgp
 
 extern "C" {
@@ -50,7 +43,7 @@ hipError_t bsgp_c512_launch_persist(const void* a, int K, size_t lds, hipStream_
 hipError_t bsgp_c512_persist_resident(const void* a, int K, size_t lds, int* per_cu) {
   const bsgp_c512::SolveArgs& A = *static_cast<const bsgp_c512::SolveArgs*>(a);
   bool adapt = false;
-  const int mode = bsgp_c512::persist_mode_coop(A, &adapt);
+  const int mode = bsgp_c512::ls_mode(A, &adapt);
   const void* f = A.storage == BSGP_STORAGE_F32
                       ? bsgp_c512::persist_kernel_coop_f32(K, mode, adapt)
                       : bsgp_c512::persist_kernel<double, true>(K, mode, adapt);

@@ -12,9 +12,11 @@
 #include <type_traits>
 #include <vector>
 
-// pass 1 of the line search also sums the second trial (as in the float64
-// persistent build, bsgp_persist.hip: the two stay bitwise equal; the
-// cooperative kernels of this unit keep it off, bsgp_kernels.hpp)
+// pass 1 of the line search also sums the second trial, in this unit's
+// per-wave float64 phase kernels and in the per-wave float64 persistent build
+// (bsgp_persist.hip): those two stay bitwise equal.  No other unit turns it
+// on (bsgp_kernels.hpp), so the application-size persistent build
+// (bsgp_persist_app.hip) is not bitwise equal to these phase kernels.
 #ifndef BSGP_LS1_K2
 #define BSGP_LS1_K2 1
 #endif
@@ -32,7 +34,7 @@ hipError_t phase_prof(unsigned long long* out, int n, int reset) {
     e = hipMemcpyToSymbol(HIP_SYMBOL(g_phase), z, sizeof z);
   }
   // the cooperative 512-thread build keeps its own counters: add them
-  if (e == hipSuccess && BSGP_COOP512) {
+  if (e == hipSuccess) {
     unsigned long long c[kPhaseSlots] = {};
     e = bsgp_c512_phase_prof(c, n, reset);
     if (e == hipSuccess && out)
@@ -278,28 +280,25 @@ __global__ void grad_parts_kernel(int64_t n, const double* den, const double* gn
 }
 
 // ----------------------------------------------------------- launchers
-// Kernels come in two builds: per-wave transforms (COOP = false) and, for long
-// rows/columns (Geo::coop), workgroup-cooperative ones; separate instantiations
-// keep each build's register allocation its own.
-// ----------------------------------------------------------- launchers
+// The solver's phase kernels come in two builds: per-wave transforms (this
+// unit and bsgp_solver_f32.hip, 256 threads) and, for long rows/columns
+// (Geo::coop), workgroup-cooperative ones with 512 threads
+// (bsgp_solver_c512.hip).
 hipError_t launch_setup(const SolveArgs& a, size_t lds, hipStream_t s) {
-  if (a.g.coop && BSGP_COOP512) return bsgp_c512_launch_setup(&a, lds, s);
+  if (a.g.coop) return bsgp_c512_launch_setup(&a, lds, s);
   if (a.storage == BSGP_STORAGE_F32) return launch_setup_f32(a, lds, s);
-  return a.g.coop ? launch_setup_t<true, double>(a, lds, s) : launch_setup_t<false, double>(a, lds, s);
+  return launch_setup_t<false, double>(a, lds, s);
 }
 hipError_t launch_iteration(const SolveArgs& a, int K, size_t lds, hipStream_t s, hipEvent_t* ev) {
-  if (a.g.coop && BSGP_COOP512) return bsgp_c512_launch_iteration(&a, K, lds, s, ev);
+  if (a.g.coop) return bsgp_c512_launch_iteration(&a, K, lds, s, ev);
   if (a.storage == BSGP_STORAGE_F32) return launch_iteration_f32(a, K, lds, s, ev);
-  return a.g.coop ? launch_iteration_t<true, double>(a, K, lds, s, ev)
-                  : launch_iteration_t<false, double>(a, K, lds, s, ev);
+  return launch_iteration_t<false, double>(a, K, lds, s, ev);
 }
 hipError_t team_resident_per_cu(bool coop, int storage, size_t lds, int* per_cu) {
-  if (coop && BSGP_COOP512) return bsgp_c512_team_resident(storage, lds, per_cu);
+  if (coop) return bsgp_c512_team_resident(storage, lds, per_cu);
   std::vector<const void*> fns;
   if (storage == BSGP_STORAGE_F32)
-    solver_kernels_f32(fns, coop);
-  else if (coop)
-    solver_kernels<true, double>(fns);
+    solver_kernels_f32(fns);
   else
     solver_kernels<false, double>(fns);
   return team_resident(fns, lds, per_cu);
@@ -413,7 +412,7 @@ hipError_t set_solver_lds_limit(size_t bytes) {
   std::lock_guard<std::mutex> lock(mu);
   if (applied[dev] >= bytes) return hipSuccess;
   std::vector<const void*> fns = {
-      (const void*)k_col<false>, (const void*)k_col<true>,
+      (const void*)k_col<false>,
       (const void*)apply_op_kernel<false>, (const void*)apply_op_kernel<true>,
       (const void*)tf_rows_kernel<false>, (const void*)tf_rows_kernel<true>,
       (const void*)tf_cols_kernel<false>, (const void*)tf_cols_kernel<true>,
@@ -421,16 +420,14 @@ hipError_t set_solver_lds_limit(size_t bytes) {
       (const void*)op_cols_kernel<false>, (const void*)op_cols_kernel<true>,
       (const void*)op_rows_inv_kernel<false>, (const void*)op_rows_inv_kernel<true>};
   solver_kernels<false, double>(fns);
-  solver_kernels<true, double>(fns);
-  solver_kernels_f32(fns, false);
-  solver_kernels_f32(fns, true);
+  solver_kernels_f32(fns);
   persist_kernels_all(fns);
   for (const void* f : fns) {
     hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
     if (e != hipSuccess) return e;
   }
-  hipError_t e = BSGP_COOP512 ? bsgp_c512_set_lds_limit(bytes) : hipSuccess;
-  if (e == hipSuccess && BSGP_COOP512) e = bsgp_c512_persist_set_lds_limit(bytes);
+  hipError_t e = bsgp_c512_set_lds_limit(bytes);
+  if (e == hipSuccess) e = bsgp_c512_persist_set_lds_limit(bytes);
   if (e == hipSuccess) e = bsgp_app_persist_set_lds_limit(bytes);
   if (e == hipSuccess) applied[dev] = bytes;
   return e;

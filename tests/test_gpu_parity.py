@@ -377,7 +377,7 @@ def test_c4_group_leader_team_sizes(sgpmod, T):
     """C4's field (2048^2, cooperative plan) at explicit team sizes around
     the flag-barrier cutover: 64 members take the flat flag
     barriers, 65 / 100 / 255 the eight group leaders with uneven groups
-    (T % 8 = 1, 4, 7; 255 also polls wide reductions, BSGP_RED_POLL_MAX).
+    (T % 8 = 1, 4, 7; 255 also polls wide reductions, kRedPollMax).
     The team size used is reported, no barrier timed out, and the discrepancy
     of the reference's own C4 run (make_golden.py c4) is met at every one of
     three iterations."""

@@ -19,8 +19,7 @@ stay at or under its budget.  What each allowance is:
   image).  C3's kernel: setup 344 B + 32 = 376 B; line search 292 B.
 * the cooperative (512-thread, 2 waves/SIMD) line search k_ls<.., COOP>:
   2-41 VGPR spills at the 256-VGPR cap (C4's phase kernels).
-* the per-wave phase line search k_ls<..> and k_setup<false, ..> (and the
-  256-thread cooperative k_setup<true, ..>, off the bench paths): a 36-B
+* the per-wave phase line search k_ls<..> and k_setup<false, ..>: a 36-B
   frame that no instruction of the kernel addresses (no scratch_* or
   buffer access in its code; checked in the ISA, profiles/r06/regbudget.txt).
 * psf_stamps_kernel: the DIAPL coefficient arrays of one stamp (runs once
@@ -50,9 +49,6 @@ ALLOW = [
     (r"^_ZN9bsgp_c5124k_lsILi1ELin1ELb1ELb1E", 41, 144),
     (r"^_ZN4bsgp4k_lsILi\d+ELi(0|3|4|n1)ELb0ELb0E[df]", 0, 36),
     (r"^_ZN4bsgp7k_setupILb0E[df]", 0, 36),
-    # the 256-thread cooperative setup (only when BSGP_COOP512 is off; the
-    # cooperative plans run bsgp_c512::k_setup): the same unaddressed 36-B frame
-    (r"^_ZN4bsgp7k_setupILb1E[df]", 0, 36),
     # C4's cooperative setup (once per solve): the same unaddressed 36-B frame
     # since round 6's DPP / swizzle wave reductions (checked in the ISA: no
     # scratch or buffer instruction in the kernel)
