@@ -86,6 +86,36 @@ class PsfModel(ctypes.Structure):
                 ("ncoef", ctypes.c_int32)]
 
 
+BSGP_STATE_MAGIC = 0x53475342
+BSGP_STATE_VERSION = 1
+BSGP_STATE_HEADER_BYTES = 1024
+
+
+class StateHeader(ctypes.Structure):
+    """bsgp_state_header (include/bsgp.h): the first bytes of a solver-state record."""
+    _fields_ = [
+        ("magic", ctypes.c_uint32), ("version", ctypes.c_uint32),
+        ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("storage", ctypes.c_int32),
+        ("conv_mode", ctypes.c_int32), ("hist_cap", ctypes.c_int32), ("T", ctypes.c_int32),
+        ("iters_done", ctypes.c_int32), ("stopped", ctypes.c_int32), ("Xones", ctypes.c_int32),
+        ("epoch", ctypes.c_int32), ("g32", ctypes.c_int32), ("beta0_given", ctypes.c_int32),
+        ("record_bytes", ctypes.c_int64), ("counters", ctypes.c_int64 * 7),
+        ("scaling", ctypes.c_double), ("flux", ctypes.c_double), ("bkg_scalar", ctypes.c_double),
+        ("x_low", ctypes.c_double), ("x_upp", ctypes.c_double), ("Dcoeff", ctypes.c_double),
+        ("tol", ctypes.c_double), ("elapsed", ctypes.c_double), ("fv", ctypes.c_double),
+        ("alpha", ctypes.c_double), ("tau", ctypes.c_double), ("lr", ctypes.c_double),
+        ("init_lr", ctypes.c_double), ("beta", ctypes.c_double), ("lam_p", ctypes.c_double),
+        ("lam_ratio", ctypes.c_double), ("kappa", ctypes.c_double), ("konst", ctypes.c_double),
+        ("gfill", ctypes.c_double), ("Valpha", ctypes.c_double * 32),
+        ("Fold", ctypes.c_double * 32), ("prm", Params),
+    ]
+
+
+assert ctypes.sizeof(StateHeader) <= BSGP_STATE_HEADER_BYTES
+STATE_HEADER_DTYPE = np.dtype(StateHeader)
+# sections of a record after the header, in bsgp_state_layout's order (offs[1:])
+STATE_SECTIONS = ("discr", "crit", "times", "flags", "x", "g", "x_tf", "pw", "gn", "bkg")
+
 _lib = None
 _lib_lock = threading.Lock()
 
@@ -123,13 +153,18 @@ def lib():
             L.bsgp_fits_to_f64.argtypes = [vp, i64, i32, dbl, dbl, vp, vp]
             L.bsgp_psf_stamps.argtypes = [ctypes.POINTER(PsfModel), vp, i32, i32, i32, vp, vp]
             L.bsgp_plan_set_psfs.argtypes = [vp, vp, i32, vp]
+            L.bsgp_state_layout.argtypes = [i32, i32, i32, i32, i32, vp]
+            L.bsgp_state_bytes.argtypes = [vp, i32, i32, ctypes.POINTER(i64)]
+            L.bsgp_state_save.argtypes = [vp, i32, vp, i64, vp]
+            L.bsgp_solve_resume.argtypes = [vp, i32, vp, vp, i32, i64, vp, vp, vp]
             for name in ["bsgp_plan_create", "bsgp_plan_create_checked", "bsgp_plan_destroy", "bsgp_plan_info",
                          "bsgp_solve_device", "bsgp_solve_host", "bsgp_solve_profiled",
                          "bsgp_apply_operator",
                          "bsgp_project_df", "bsgp_beta_div", "bsgp_beta_div_deriv",
                          "bsgp_beta_div_grad_parts", "bsgp_device_synchronize",
                          "bsgp_extract_tiles", "bsgp_coadd_tiles", "bsgp_fits_to_f64",
-                         "bsgp_psf_stamps", "bsgp_plan_set_psfs"]:
+                         "bsgp_psf_stamps", "bsgp_plan_set_psfs", "bsgp_state_layout",
+                         "bsgp_state_bytes", "bsgp_state_save", "bsgp_solve_resume"]:
                 getattr(L, name).restype = ctypes.c_int
             if L.bsgp_abi_version() != ABI_VERSION:
                 raise BsgpError(-3, f"{LIB_PATH} has ABI {L.bsgp_abi_version()}, this binding "
@@ -142,7 +177,8 @@ EXPORTED = ["bsgp_plan_create", "bsgp_plan_create_checked", "bsgp_plan_destroy",
             "bsgp_solve_host", "bsgp_solve_profiled", "bsgp_apply_operator", "bsgp_project_df", "bsgp_beta_div",
             "bsgp_beta_div_deriv", "bsgp_beta_div_grad_parts", "bsgp_device_synchronize",
             "bsgp_last_error", "bsgp_abi_version", "bsgp_extract_tiles", "bsgp_coadd_tiles",
-            "bsgp_fits_to_f64", "bsgp_psf_stamps", "bsgp_plan_set_psfs"]
+            "bsgp_fits_to_f64", "bsgp_psf_stamps", "bsgp_plan_set_psfs", "bsgp_state_layout",
+            "bsgp_state_bytes", "bsgp_state_save", "bsgp_solve_resume"]
 
 
 def check(rc):
@@ -279,6 +315,7 @@ class Plan:
         outs = Outputs(*[_ptr(out[k]) for k in ["x", "iters", "discr", "times", "crit", "flags",
                                                  "beta_final", "counters", "err", "x_iter"]])
         self._keep = (gn, bkg, flux, x0, beta0, obj)
+        self._last = (B, int(params.MAXIT), int(params.bkg_is_map), out)
         if profile:
             kms = np.zeros(6, np.float64)
             nl = np.zeros(6, np.int64)
@@ -290,6 +327,302 @@ class Plan:
         check(lib().bsgp_solve_device(self.h, B, ctypes.byref(params), ctypes.byref(ins),
                                       ctypes.byref(outs), current_stream()))
         return out
+
+    # ------------------------------------------------------- save and resume
+    def save_state(self, B):
+        """The solver state the last solve / resume of B images left on this
+        plan, as a [B, bytes] uint8 CUDA tensor of records (bsgp_state_save).
+        Call it before anything else solves on the plan.  Asynchronous."""
+        last = getattr(self, "_last", None)
+        if last is None or last[0] != B:
+            raise BsgpError(BSGP_ERR_ARG, "save_state: no solve of this batch size ran on the plan")
+        _, maxit, bmap, _ = last
+        nb = ctypes.c_int64()
+        check(lib().bsgp_state_bytes(self.h, bmap, maxit, ctypes.byref(nb)))
+        rec = torch.empty((B, nb.value), dtype=torch.uint8, device="cuda")
+        check(lib().bsgp_state_save(self.h, B, _ptr(rec), nb.value, current_stream()))
+        return rec
+
+    def resume(self, state, params, index=None, want_times=True):
+        """Continue records (a [n, bytes] uint8 CUDA tensor) up to params.MAXIT
+        (bsgp_solve_resume): image i of the result is record index[i] (an int32
+        CUDA tensor) or record i.  Returns the dict of :meth:`solve`."""
+        n = state.shape[0]
+        B = n if index is None else int(index.numel())
+        M1 = params.MAXIT + 1
+        dev = state.device
+        f64 = dict(dtype=torch.float64, device=dev)
+        d64 = torch.zeros(B * M1 * (2 + bool(want_times)) + B, **f64)
+        i32 = torch.zeros(B * (M1 + 1) + 2 * 8 * B, dtype=torch.int32, device=dev)
+        parts = iter(torch.split(d64, [B * M1] * (2 + bool(want_times)) + [B]))
+        discr, crit = next(parts).view(B, M1), next(parts).view(B, M1)
+        times = next(parts).view(B, M1) if want_times else None
+        beta_final = next(parts)
+        cnt, iters, flags = torch.split(i32, [2 * 8 * B, B, B * M1])
+        out = {
+            "x": torch.empty((B, self.H, self.W), **f64),
+            "iters": iters, "discr": discr, "times": times, "crit": crit,
+            "flags": flags.view(B, M1), "beta_final": beta_final,
+            "counters": cnt.view(torch.int64).view(B, 8), "err": None, "x_iter": None,
+        }
+        outs = Outputs(*[_ptr(out[k]) for k in ["x", "iters", "discr", "times", "crit", "flags",
+                                                 "beta_final", "counters", "err", "x_iter"]])
+        self._keep = (state, index)
+        check(lib().bsgp_solve_resume(self.h, B, ctypes.byref(params), _ptr(state), n,
+                                      state.shape[1], _ptr(index), ctypes.byref(outs),
+                                      current_stream()))
+        self._last = (B, int(params.MAXIT), int(params.bkg_is_map), out)
+        return out
+
+
+def state_layout(H, W, storage, bkg_is_map, hist_cap):
+    """Byte offsets of a solver-state record (bsgp_state_layout; needs no
+    device): {'bytes': record bytes, 'discr': ..., ..., 'bkg': 0 without a map}."""
+    offs = np.zeros(11, np.int64)
+    check(lib().bsgp_state_layout(int(H), int(W), int(storage), int(bool(bkg_is_map)),
+                                  int(hist_cap), offs.ctypes.data))
+    return dict(zip(("bytes",) + STATE_SECTIONS, (int(v) for v in offs)))
+
+
+class SolverState:
+    """The state of a batched solve after its last iteration: one fixed-size
+    record per image (include/bsgp.h, bsgp_state_header + sections) plus the
+    PSF that finds the plan again.  ``records`` is a [B, bytes] uint8 array, on
+    the host (numpy) or on the device (CUDA tensor).  A resume needs nothing
+    else: not the observed images, not the original keyword arguments."""
+
+    def __init__(self, records, psf):
+        self.records = records
+        self.psf = np.ascontiguousarray(psf)
+        self._hdr = None
+
+    # ------------------------------------------------------------- accessors
+    @property
+    def on_device(self):
+        return torch is not None and torch.is_tensor(self.records)
+
+    @property
+    def header(self):
+        """The record headers as a numpy structured array (STATE_HEADER_DTYPE)."""
+        if self._hdr is None:
+            n = STATE_HEADER_DTYPE.itemsize
+            h = self.records[:, :n]
+            h = h.cpu().numpy() if self.on_device else np.ascontiguousarray(h)
+            self._hdr = h.reshape(-1).view(STATE_HEADER_DTYPE).copy()
+        return self._hdr
+
+    def __len__(self):
+        return int(self.records.shape[0])
+
+    @property
+    def iters_done(self):
+        return self.header["iters_done"].copy()
+
+    @property
+    def stopped(self):
+        """True where the solve has ended (a stop rule or the setup stopped the
+        image): a resume leaves those images as they are."""
+        return self.header["stopped"] != 0
+
+    @property
+    def shape(self):
+        h = self.header[0]
+        return int(h["H"]), int(h["W"])
+
+    @property
+    def layout(self):
+        h = self.header[0]
+        return state_layout(h["H"], h["W"], h["storage"], h["prm"]["bkg_is_map"], h["hist_cap"])
+
+    def params(self):
+        """The ``Params`` of the solve the records come from."""
+        return Params.from_buffer_copy(self.header[0]["prm"].tobytes())
+
+    def field(self, name):
+        """Section ``name`` of every record as a host array: discr / crit /
+        times [B, hist_cap] float64, flags int32, x / g / x_tf / pw [B, H, W]
+        in the storage type, gn / bkg [B, H, W] float64 (gn: the slot's bytes,
+        see ``header['g32']``)."""
+        H, W = self.shape
+        L, h = self.layout, self.header[0]
+        rec = self.to_host().records
+        if name in ("discr", "crit", "times", "flags"):
+            dt, n, shp = (np.int32 if name == "flags" else np.float64), int(h["hist_cap"]), None
+        else:
+            vec = name in ("x", "g", "x_tf", "pw")
+            dt = np.float32 if (vec and h["storage"] == BSGP_STORAGE_F32) else np.float64
+            n, shp = H * W, (len(self), H, W)
+        if name == "bkg" and not L["bkg"]:
+            return None
+        nb = n * np.dtype(dt).itemsize
+        a = np.ascontiguousarray(rec[:, L[name]:L[name] + nb]).view(dt)
+        return a.reshape(shp) if shp else a
+
+    def __getitem__(self, idx):
+        """Subset / permutation of the images (an index array, a slice or an int)."""
+        if isinstance(idx, (int, np.integer)):
+            idx = [int(idx)]
+        if isinstance(idx, slice):
+            idx = np.arange(len(self))[idx]
+        idx = np.asarray(idx)
+        if idx.dtype == bool:
+            idx = np.nonzero(idx)[0]
+        idx = idx.astype(np.int64)
+        rec = (self.records[torch.as_tensor(idx, device=self.records.device)] if self.on_device
+               else self.records[idx])
+        return SolverState(rec, self.psf)
+
+    # ------------------------------------------------------- host and device
+    def to_host(self):
+        if not self.on_device:
+            return self
+        s = SolverState(self.records.cpu().numpy(), self.psf)
+        return s
+
+    def to_device(self):
+        if self.on_device:
+            return self
+        require_gpu()
+        return SolverState(torch.from_numpy(np.ascontiguousarray(self.records)).to("cuda"),
+                           self.psf)
+
+    # ------------------------------------------------------------------ disk
+    def save(self, path):
+        """One .npz: the records, the PSF and the layout version."""
+        h = self.to_host()
+        with open(path, "wb") as f:
+            np.savez(f, records=h.records, psf=h.psf,
+                     version=np.int64(BSGP_STATE_VERSION),
+                     shape=np.asarray(h.shape, np.int64))
+
+    @classmethod
+    def load(cls, path):
+        with np.load(path) as z:
+            if int(z["version"]) != BSGP_STATE_VERSION:
+                raise ValueError(f"{path}: solver-state layout version {int(z['version'])}, "
+                                 f"this library reads version {BSGP_STATE_VERSION}")
+            rec, psf, shape = z["records"], z["psf"], tuple(int(v) for v in z["shape"])
+        s = cls(rec, psf)
+        s.validate(shape)
+        return s
+
+    def validate(self, shape=None):
+        """Raise ValueError unless every record carries the magic number, this
+        library's layout version, one shape (``shape`` if given) and the size
+        its own header implies."""
+        rec = self.records
+        if rec.ndim != 2 or rec.shape[0] < 1 or rec.shape[1] < BSGP_STATE_HEADER_BYTES:
+            raise ValueError("solver state: records must be [B, bytes] uint8")
+        h = self.header
+        if np.any(h["magic"] != BSGP_STATE_MAGIC):
+            raise ValueError("solver state: bad magic number (not a solver-state record)")
+        if np.any(h["version"] != BSGP_STATE_VERSION):
+            raise ValueError(f"solver state: layout version {int(h['version'][0])}, this library "
+                             f"reads version {BSGP_STATE_VERSION}")
+        H, W = self.shape
+        if np.any(h["H"] != H) or np.any(h["W"] != W) or (shape is not None
+                                                         and tuple(shape) != (H, W)):
+            raise ValueError(f"solver state: shape mismatch (records {H}x{W}, expected {shape})")
+        if np.any(h["record_bytes"] != rec.shape[1]) or self.layout["bytes"] != rec.shape[1]:
+            raise ValueError("solver state: record size does not match its header (shape, "
+                             "storage, hist_cap)")
+
+    # ----------------------------------------------------------- construction
+    @classmethod
+    def from_arrays(cls, psf, params, x, g, x_tf, gn, *, iters_done, alpha, tau, fv, flux,
+                    scaling, x_low, x_upp, tol, Valpha, Fold, pw=None, bkg=0.0, beta=None,
+                    lr=None, init_lr=None, epoch=None, konst=0.0, Xones=False, stopped=0,
+                    lam_p=0.0, lam_ratio=0.0, kappa=0.0, elapsed=0.0, counters=None, discr=None,
+                    crit=None, times=None, flags=None, hist_cap=None, team=1,
+                    conv_mode=BSGP_CONV_CIRCULAR, storage="f64", beta0_given=False):
+        """Records from explicit arrays and scalars (the teacher-forced tests:
+        a state captured in the reference, continued on the device).
+
+        Vectors are [B, H, W] (or [H, W] for one image) in *scaled* units, as
+        the loop carries them: ``x`` the iterate, ``g`` its gradient, ``x_tf``
+        = A(x), ``gn`` the scaled observed image with its null pixels filled,
+        ``pw`` = (x_tf + bkg)**(beta - 1) for the beta objective, ``bkg`` a
+        scalar per image or a [B, H, W] map.  Scalars are per image ([B] or
+        broadcast): ``iters_done`` completed iterations, the step length
+        ``alpha``, ``tau``, the objective ``fv`` at x, ``flux``, ``scaling``,
+        the scaling-matrix bounds ``x_low`` / ``x_upp``, the stop tolerance
+        ``tol``, the memories ``Valpha`` [B, M_alpha] and ``Fold`` [B, M],
+        ``beta`` / ``lr`` / ``init_lr`` / ``epoch`` (default: params.betaParam,
+        params.lr, params.lr, iters_done), ``konst`` the lambda-independent
+        objective sum at beta (sum s*gn**beta over sum gn; 0 for KL), ``Xones``
+        (the scaling matrix is still ones).  ``params`` is the ``Params`` of the
+        solve; history rows (discr, crit, times, flags: [B, iters_done + 1])
+        default to zeros."""
+        x = np.asarray(x, np.float64)
+        if x.ndim == 2:
+            x = x[None]
+        Bn, H, W = x.shape
+        N = H * W
+        sc = storage_code(storage)
+        vdt = np.float32 if sc == BSGP_STORAGE_F32 else np.float64
+        done = np.broadcast_to(np.asarray(iters_done, np.int64), (Bn,))
+        cap = int(hist_cap) if hist_cap is not None else int(done.max()) + 1
+        bkg = np.asarray(bkg, np.float64)
+        bmap = bkg.ndim >= 2
+        prm = Params.from_buffer_copy(bytes(params))
+        prm.bkg_is_map = int(bmap)
+        L = state_layout(H, W, sc, bmap, cap)
+        rec = np.zeros((Bn, L["bytes"]), np.uint8)
+        hdr = np.zeros(Bn, STATE_HEADER_DTYPE)
+
+        def per(v, dt=np.float64):
+            return np.broadcast_to(np.asarray(v, dt), (Bn,))
+
+        hdr["magic"], hdr["version"] = BSGP_STATE_MAGIC, BSGP_STATE_VERSION
+        hdr["H"], hdr["W"], hdr["storage"], hdr["conv_mode"] = H, W, sc, conv_mode
+        hdr["hist_cap"], hdr["T"], hdr["iters_done"] = cap, team, done
+        hdr["stopped"], hdr["Xones"] = per(stopped, np.int32), per(Xones, np.int32)
+        hdr["epoch"] = done if epoch is None else per(epoch, np.int32)
+        hdr["beta0_given"] = int(bool(beta0_given))
+        hdr["record_bytes"] = L["bytes"]
+        if counters is not None:
+            hdr["counters"] = np.broadcast_to(np.asarray(counters, np.int64), (Bn, 7))
+        hdr["scaling"], hdr["flux"] = per(scaling), per(flux)
+        hdr["bkg_scalar"] = 0.0 if bmap else per(bkg)
+        hdr["x_low"], hdr["x_upp"], hdr["tol"] = per(x_low), per(x_upp), per(tol)
+        hdr["Dcoeff"] = 2 / float(N) * per(scaling)
+        hdr["elapsed"], hdr["fv"], hdr["alpha"], hdr["tau"] = per(elapsed), per(fv), per(alpha), per(tau)
+        hdr["lr"] = per(prm.lr if lr is None else lr)
+        hdr["init_lr"] = per(prm.lr if init_lr is None else init_lr)
+        hdr["beta"] = per(prm.betaParam if beta is None else beta)
+        hdr["lam_p"], hdr["lam_ratio"], hdr["kappa"] = per(lam_p), per(lam_ratio), per(kappa)
+        hdr["konst"] = per(konst)
+        va = np.broadcast_to(np.asarray(Valpha, np.float64), (Bn, prm.M_alpha))
+        fo = np.broadcast_to(np.asarray(Fold, np.float64), (Bn, prm.M))
+        hdr["Valpha"][:, :prm.M_alpha] = va
+        hdr["Fold"][:, :prm.M] = fo
+        hdr["prm"] = np.frombuffer(bytes(prm), STATE_HEADER_DTYPE["prm"])[0]
+        rec[:, :STATE_HEADER_DTYPE.itemsize] = hdr.view(np.uint8).reshape(Bn, -1)
+
+        def put(name, a, dt):
+            if a is None:
+                return
+            a = np.ascontiguousarray(np.broadcast_to(np.asarray(a, dt), (Bn, H, W))
+                                     if name in ("x", "g", "x_tf", "pw", "gn", "bkg")
+                                     else np.asarray(a, dt).reshape(Bn, -1))
+            b = a.reshape(Bn, -1).view(np.uint8)
+            rec[:, L[name]:L[name] + b.shape[1]] = b
+
+        put("x", x, vdt)
+        put("g", g, vdt)
+        put("x_tf", x_tf, vdt)
+        put("pw", pw, vdt)
+        put("gn", gn, np.float64)
+        if bmap:
+            put("bkg", bkg, np.float64)
+        for name, a in (("discr", discr), ("crit", crit), ("times", times)):
+            if a is not None:
+                put(name, np.asarray(a, np.float64)[..., :cap], np.float64)
+        if flags is not None:
+            put("flags", np.asarray(flags, np.int32)[..., :cap], np.int32)
+        s = cls(rec, psf)
+        s.validate()
+        return s
 
 
 STATUS_LS_CAP = 1

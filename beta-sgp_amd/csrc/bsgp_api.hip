@@ -205,6 +205,12 @@ struct bsgp_plan_s {
   // persistent solver: dequeue counter + per-image published iterations
   unsigned* pq = nullptr;
   size_t pq_n = 0;
+  // the last solve on this plan, for bsgp_state_save: its parameters, output
+  // buffers, batch and team size (valid until the next solve overwrites the slots)
+  bool last_valid = false;
+  bsgp_params last_prm{};
+  bsgp_outputs last_out{};
+  int last_B = 0, last_T = 0, last_beta0 = 0;
 };
 
 // Capacity of one thread's projection list: the pixels it streams in one pass
@@ -776,8 +782,20 @@ struct SolveProf {
   int64_t* launches;
 };
 
+// A resumed solve (bsgp_solve_resume): k_state_load takes the place of the
+// setup, and the iteration loop goes on where the records stopped.
+struct ResumeCtx {
+  StateArgs sa;     // the records (rec, rec_bytes, index, L, hist_cap); solve_impl adds the plan's part
+  int T;            // the records' team size
+  int it0;          // first iteration to launch: the fewest iterations done + 1
+  bool uniform;     // every image that goes on has done `done_it` iterations
+  int done_it;
+  int beta0_given;  // the records' solve had per-image betas (picks the line-search build)
+};
+
 static int solve_impl(bsgp_plan p, int32_t B, const bsgp_params* prm, const bsgp_inputs* in,
-                      const bsgp_outputs* out, void* stream, SolveProf* prof);
+                      const bsgp_outputs* out, void* stream, SolveProf* prof,
+                      const ResumeCtx* rs = nullptr);
 
 int bsgp_solve_device(bsgp_plan p, int32_t B, const bsgp_params* prm, const bsgp_inputs* in,
                       const bsgp_outputs* out, void* stream) {
@@ -810,28 +828,39 @@ int bsgp_solve_profiled(bsgp_plan p, int32_t B, const bsgp_params* prm, const bs
 }
 
 static int solve_impl(bsgp_plan p, int32_t B, const bsgp_params* prm, const bsgp_inputs* in,
-                      const bsgp_outputs* out, void* stream, SolveProf* prof) {
+                      const bsgp_outputs* out, void* stream, SolveProf* prof,
+                      const ResumeCtx* rs) {
   if (!p) return fail(BSGP_ERR_ARG, "plan is NULL");
   int rc = check_params(prm);
   if (rc) return rc;
   if (B < 1) return fail(BSGP_ERR_ARG, "B must be >= 1");
-  if (!in || !in->gn || !in->bkg) return fail(BSGP_ERR_ARG, "inputs gn/bkg missing");
-  if ((prm->init_recon == 1 || prm->scale_data == 2) && !in->x0)
-    return fail(BSGP_ERR_ARG, "init_recon=1 and scale_data=2 need x0");
+  if (!rs) {
+    if (!in || !in->gn || !in->bkg) return fail(BSGP_ERR_ARG, "inputs gn/bkg missing");
+    if ((prm->init_recon == 1 || prm->scale_data == 2) && !in->x0)
+      return fail(BSGP_ERR_ARG, "init_recon=1 and scale_data=2 need x0");
+  }
   if (!out || !out->x || !out->iters || !out->discr) return fail(BSGP_ERR_ARG, "outputs missing");
-  if (out->err && !in->obj) return fail(BSGP_ERR_ARG, "err needs the ground truth obj");
+  if (out->err && (!in || !in->obj)) return fail(BSGP_ERR_ARG, "err needs the ground truth obj");
   if (p->n_tf > 1 && B != p->n_tf)
     return fail(BSGP_ERR_ARG, "the plan holds one PSF per image: B must equal its PSF count");
   DEVICE_SCOPE(p->device);
   rc = ensure_ws(p, (size_t)B);
   if (rc) return rc;
-  const int T = choose_team(p, B, prm->team);
+  const int T = rs ? rs->T : choose_team(p, B, prm->team);
   rc = ensure_team(p, (size_t)B, T);
   if (rc) return rc;
   SolveArgs a;
   a.g = p->g;
   a.prm = *prm;
-  a.in = *in;
+  if (rs) {
+    // no inputs: the records hold what the iterations read.  The kernels read
+    // in.beta0 in the setup only; the launchers ask whether it was given
+    // (ls_mode), so a resumed solve of per-image betas points it at the state.
+    a.in = bsgp_inputs{};
+    if (rs->beta0_given) a.in.beta0 = reinterpret_cast<const double*>(p->st);
+  } else {
+    a.in = *in;
+  }
   a.out = *out;
   a.B = B;
   a.img0 = 0;
@@ -902,14 +931,18 @@ static int solve_impl(bsgp_plan p, int32_t B, const bsgp_params* prm, const bsgp
   // 375^2 / 450^2 subdivisions) the 512-thread build's thread-group transforms
   // (bsgp_persist_c512.hip); it overlaps the phases of different images itself,
   // so it runs the whole batch as one sub-batch
-  const bool persist = prm->persistent && T == 1 && !track;
+  // (a resumed slot-order solve needs every image at the same iteration; records
+  // that are not take the phase kernels, which are bit-identical)
+  const bool ring_rule = prm->stop_criterion >= 2 && prm->stop_criterion <= 4;
+  const bool persist =
+      prm->persistent && T == 1 && !track && (!rs || ring_rule || rs->uniform);
   if (persist) S = 1;
   // fixed-length persistent solves run every image's setup as the first task
   // of its chain inside k_persist: the setups of the last images overlap the
   // first iterations of the others, with no k_setup launch and no boundary
   // (BSGP_FOLD_SETUP=0: k_setup first, for A/B)
   const bool ring = prm->stop_criterion >= 2 && prm->stop_criterion <= 4;
-  a.fold_setup = (persist && !ring && env_knob("BSGP_FOLD_SETUP", 1, 0, 1)) ? 1 : 0;
+  a.fold_setup = (persist && !ring && !rs && env_knob("BSGP_FOLD_SETUP", 1, 0, 1)) ? 1 : 0;
   // sub-batch 0 runs on the caller's stream itself, sub-batches 1..S-1 on the
   // plan's streams: S streams in all, so S = 4 fits the 4 hardware queues HIP
   // opens per process (GPU_MAX_HW_QUEUES)
@@ -924,7 +957,8 @@ static int solve_impl(bsgp_plan p, int32_t B, const bsgp_params* prm, const bsgp
   // device counter of images not yet stopped: B, counted down by every image
   // the setup or k_bb stops (count_stopped); the last one writes this solve's
   // seq to the host-mapped word
-  HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)p->active, B, 1, s));
+  // (resumed: 0, counted up by k_state_load for every image that goes on)
+  HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)p->active, rs ? 0 : B, 1, s));
   a.seq = g_solve_seq.fetch_add(1, std::memory_order_relaxed) + 1;
   p->seq = a.seq;
   a.done_host = p->done_d;
@@ -934,6 +968,28 @@ static int solve_impl(bsgp_plan p, int32_t B, const bsgp_params* prm, const bsgp
   if (T > 1 && (T <= kTeamFlags || T >= 8))
     HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)p->tpart, kPartEmptyWord,
                               B * kPartBufs * (size_t)(T + 8) * kMaxRed * 2, s));
+  p->last_valid = true;
+  p->last_prm = *prm;
+  p->last_out = *out;
+  p->last_B = B;
+  p->last_T = T;
+  p->last_beta0 = a.in.beta0 != nullptr;
+  StateArgs ld{};
+  if (rs) {
+    ld = rs->sa;
+    ld.ws = p->ws;
+    ld.slot_stride = p->slot_stride;
+    ld.vec_stride = p->vec_stride;
+    ld.st = p->st;
+    ld.T = T;
+    ld.M1 = prm->MAXIT + 1;
+    ld.out = *out;
+    ld.prm = *prm;
+    ld.active = p->active;
+    HIP_TRY(launch_state_load(ld, B, s));
+    if (!(persist && !ring))
+      HIP_TRY(launch_state_post(ld, B, nullptr, nullptr, 0, p->done_d, a.seq, s));
+  }
   hipStream_t ss[bsgp_plan_s::kMaxStreams];
   SolveArgs sa[bsgp_plan_s::kMaxStreams];
   if (S > 1) HIP_TRY(hipEventRecord(p->ev_fork, s));
@@ -944,7 +1000,7 @@ static int solve_impl(bsgp_plan p, int32_t B, const bsgp_params* prm, const bsgp
     sa[j].img0 = (int)((int64_t)B * j / S);
     sa[j].nimg = (int)((int64_t)B * (j + 1) / S) - sa[j].img0;
     if (prof) HIP_TRY(hipEventRecord(prof->ev[0], ss[j]));
-    if (!a.fold_setup) HIP_TRY(launch_setup(sa[j], p->lds_bytes, ss[j]));
+    if (!a.fold_setup && !rs) HIP_TRY(launch_setup(sa[j], p->lds_bytes, ss[j]));
     if (prof) HIP_TRY(hipEventRecord(prof->ev[1], ss[j]));
     if (track) HIP_TRY(launch_track(sa[j], 0, ss[j]));
   }
@@ -958,6 +1014,8 @@ static int solve_impl(bsgp_plan p, int32_t B, const bsgp_params* prm, const bsgp
       p->pq_n = need;
     }
     HIP_TRY(hipMemsetAsync(p->pq, 0, need * sizeof(unsigned), s));
+    if (rs && !ring)  // slot order: the queue starts at the records' iteration
+      HIP_TRY(launch_state_post(ld, B, p->pq, p->pq + 1, rs->done_it, p->done_d, a.seq, s));
     int per_cu = 0;
     HIP_TRY(persist_resident_per_cu(sa[0], K, p->lds_bytes, &per_cu));
     if (per_cu < 1) return fail(BSGP_ERR_HIP, "persistent solver does not fit a CU");
@@ -1000,7 +1058,8 @@ static int solve_impl(bsgp_plan p, int32_t B, const bsgp_params* prm, const bsgp
     for (int i = 0; i < bsgp_plan_s::kPollRing; ++i)
       if (!p->ev_it[i]) HIP_TRY(hipEventCreateWithFlags(&p->ev_it[i], hipEventDisableTiming));
   int it_run = 0;
-  for (int it = 1; it <= prm->MAXIT; ++it) {
+  const int it0 = rs ? rs->it0 : 1;
+  for (int it = it0; it <= prm->MAXIT; ++it) {
     it_run = it;
     for (int j = 0; j < S; ++j) {
       HIP_TRY(launch_iteration(sa[j], K, p->lds_bytes, ss[j],
@@ -1009,7 +1068,7 @@ static int solve_impl(bsgp_plan p, int32_t B, const bsgp_params* prm, const bsgp
     }
     if (data_stop && it < prm->MAXIT) {
       HIP_TRY(hipEventRecord(p->ev_it[it % bsgp_plan_s::kPollRing], ss[0]));
-      if (it > kLook) {
+      if (it - it0 >= kLook) {
         HIP_TRY(hipEventSynchronize(p->ev_it[(it - kLook) % bsgp_plan_s::kPollRing]));
         if (__atomic_load_n(p->done_h, __ATOMIC_ACQUIRE) == a.seq) break;
       }
@@ -1122,6 +1181,207 @@ int bsgp_solve_host(bsgp_plan p, int32_t B, const bsgp_params* prm, const bsgp_i
   cleanup();
   if (!ok) return fail(BSGP_ERR_HIP, "solve or device to host copy failed");
   return BSGP_OK;
+}
+
+// ---- solver state: save / resume (kernels in bsgp_state.hip) ---------------
+
+int bsgp_state_layout(int32_t H, int32_t W, int32_t storage, int32_t bkg_is_map,
+                      int32_t hist_cap, int64_t* offs) {
+  if (!offs) return fail(BSGP_ERR_ARG, "offs is NULL");
+  if (H < 1 || W < 1 || hist_cap < 1) return fail(BSGP_ERR_ARG, "bad shape or hist_cap");
+  if (storage != BSGP_STORAGE_F64 && storage != BSGP_STORAGE_F32)
+    return fail(BSGP_ERR_ARG, "bad storage");
+  const StateLayout L = state_layout((size_t)H * W, storage, bkg_is_map != 0, hist_cap);
+  const size_t v[11] = {L.bytes, L.discr, L.crit, L.times, L.flags, L.x,
+                        L.g,     L.xtf,   L.pw,   L.gn,    L.bkg};
+  for (int i = 0; i < 11; ++i) offs[i] = (int64_t)v[i];
+  return BSGP_OK;
+}
+
+int bsgp_state_bytes(bsgp_plan p, int32_t bkg_is_map, int32_t MAXIT_done_max,
+                     int64_t* bytes_per_image) {
+  if (!p) return fail(BSGP_ERR_ARG, "plan is NULL");
+  if (!bytes_per_image || MAXIT_done_max < 0) return fail(BSGP_ERR_ARG, "bad arguments");
+  *bytes_per_image = (int64_t)state_layout((size_t)p->g.H * p->g.W, p->storage, bkg_is_map != 0,
+                                           MAXIT_done_max + 1)
+                         .bytes;
+  return BSGP_OK;
+}
+
+int bsgp_state_save(bsgp_plan p, int32_t B, void* state_dev, int64_t bytes_per_image,
+                    void* stream) {
+  if (!p) return fail(BSGP_ERR_ARG, "plan is NULL");
+  if (!state_dev) return fail(BSGP_ERR_ARG, "state_dev is NULL");
+  if (!p->last_valid) return fail(BSGP_ERR_ARG, "no solve has run on this plan");
+  if (B != p->last_B || B > 65535)
+    return fail(BSGP_ERR_ARG, "B must be the last solve's batch size (at most 65535)");
+  const bsgp_params& q = p->last_prm;
+  if (q.stop_criterion == 2 && !p->last_out.crit)
+    return fail(BSGP_ERR_ARG, "saving a stop_criterion 2 solve needs its out->crit");
+  StateArgs a{};
+  a.N = p->g.H * p->g.W;
+  a.H = p->g.H;
+  a.W = p->g.W;
+  a.storage = p->storage;
+  a.conv_mode = p->conv_mode;
+  a.bmap = q.bkg_is_map != 0;
+  a.hist_cap = q.MAXIT + 1;
+  a.L = state_layout((size_t)a.N, a.storage, a.bmap != 0, a.hist_cap);
+  if ((int64_t)a.L.bytes != bytes_per_image)
+    return fail(BSGP_ERR_ARG, "bytes_per_image is not bsgp_state_bytes(plan, bkg_is_map, MAXIT)");
+  a.rec = static_cast<unsigned char*>(state_dev);
+  a.rec_bytes = a.L.bytes;
+  a.ws = p->ws;
+  a.slot_stride = p->slot_stride;
+  a.vec_stride = p->vec_stride;
+  a.st = p->st;
+  a.T = p->last_T;
+  a.beta0_given = p->last_beta0;
+  a.M1 = q.MAXIT + 1;
+  a.out = p->last_out;
+  a.prm = q;
+  DEVICE_SCOPE(p->device);
+  HIP_TRY(launch_state_save(a, B, (hipStream_t)stream));
+  return BSGP_OK;
+}
+
+int bsgp_solve_resume(bsgp_plan p, int32_t B, const bsgp_params* prm, const void* state_dev,
+                      int32_t n_state, int64_t bytes_per_image, const int32_t* index,
+                      const bsgp_outputs* out, void* stream) {
+  if (!p) return fail(BSGP_ERR_ARG, "plan is NULL");
+  int rc = check_params(prm);
+  if (rc) return rc;
+  if (!state_dev || n_state < 1) return fail(BSGP_ERR_ARG, "state_dev missing");
+  if (B < 1 || B > 65535 || (!index && B > n_state))
+    return fail(BSGP_ERR_ARG, "B must be in [1, 65535] and, without an index, at most n_state");
+  if (!out || !out->x || !out->iters || !out->discr) return fail(BSGP_ERR_ARG, "outputs missing");
+  if (out->err || out->x_iter)
+    return fail(BSGP_ERR_UNSUPPORTED, "err / x_iter are not available on a resumed solve");
+  if (p->n_tf > 1 && B != p->n_tf)
+    return fail(BSGP_ERR_ARG, "the plan holds one PSF per image: B must equal its PSF count");
+  if (bytes_per_image < BSGP_STATE_HEADER_BYTES || bytes_per_image % 16)
+    return fail(BSGP_ERR_ARG, "bad bytes_per_image");
+  DEVICE_SCOPE(p->device);
+  hipStream_t s = (hipStream_t)stream;
+  // the headers (and the index) on the host, for validation
+  std::vector<bsgp_state_header> hs((size_t)n_state);
+  std::vector<int32_t> idx((size_t)B);
+  HIP_TRY(hipMemcpy2DAsync(hs.data(), sizeof(bsgp_state_header), state_dev,
+                           (size_t)bytes_per_image, sizeof(bsgp_state_header), (size_t)n_state,
+                           hipMemcpyDeviceToHost, s));
+  if (index)
+    HIP_TRY(hipMemcpyAsync(idx.data(), index, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost,
+                           s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (!index)
+    for (int i = 0; i < B; ++i) idx[i] = i;
+  const size_t N = (size_t)p->g.H * p->g.W;
+  ResumeCtx rs{};
+  int min_done = -1, max_done = -1;
+  char msg[200];
+  for (int i = 0; i < B; ++i) {
+    if (idx[i] < 0 || idx[i] >= n_state) {
+      snprintf(msg, sizeof msg, "index[%d] = %d is outside the %d records", i, idx[i], n_state);
+      return fail(BSGP_ERR_ARG, msg);
+    }
+    const bsgp_state_header& h = hs[(size_t)idx[i]];
+    const bsgp_params& q = h.prm;
+    const char* bad = nullptr;
+    auto same = [](const void* a, const void* b, size_t n) { return memcmp(a, b, n) == 0; };
+#define BSGP_SAME(f) \
+  if (!bad && !same(&q.f, &prm->f, sizeof q.f)) bad = #f
+    if (h.magic != BSGP_STATE_MAGIC) bad = "magic";
+    if (!bad && h.version != BSGP_STATE_VERSION) bad = "version";
+    if (!bad && (h.H != p->g.H || h.W != p->g.W)) bad = "shape (H, W)";
+    if (!bad && h.storage != p->storage) bad = "storage";
+    if (!bad && h.conv_mode != p->conv_mode) bad = "conv_mode";
+    BSGP_SAME(variant);
+    BSGP_SAME(init_recon);
+    BSGP_SAME(proj_type);
+    BSGP_SAME(stop_criterion);
+    BSGP_SAME(M_alpha);
+    BSGP_SAME(M);
+    BSGP_SAME(max_projs);
+    BSGP_SAME(gamma);
+    BSGP_SAME(beta);
+    BSGP_SAME(alpha);
+    BSGP_SAME(alpha_min);
+    BSGP_SAME(alpha_max);
+    BSGP_SAME(tau);
+    BSGP_SAME(ccd_sat_level);
+    BSGP_SAME(betaParam);
+    BSGP_SAME(lr);
+    BSGP_SAME(lr_exp_param);
+    BSGP_SAME(tol_convergence);
+    BSGP_SAME(prescaled_scaling);
+    BSGP_SAME(prescaled_tol4);
+    BSGP_SAME(has_sat);
+    BSGP_SAME(scale_data);
+    BSGP_SAME(verbose);
+    BSGP_SAME(adapt_beta);
+    BSGP_SAME(schedule_lr);
+    BSGP_SAME(bkg_is_map);
+    BSGP_SAME(ls_series);
+    BSGP_SAME(gn_compact);
+    BSGP_SAME(gn_f32);
+    BSGP_SAME(beta0_general);
+    BSGP_SAME(flux_f32);
+#undef BSGP_SAME
+    if (!bad && (h.hist_cap < 1 || h.iters_done < 0 || h.iters_done >= h.hist_cap ||
+                 h.record_bytes != bytes_per_image ||
+                 (int64_t)state_layout(N, p->storage, q.bkg_is_map != 0, h.hist_cap).bytes !=
+                     bytes_per_image))
+      bad = "record_bytes / hist_cap";
+    if (!bad && i > 0 && (h.hist_cap != rs.sa.hist_cap || h.T != rs.T ||
+                          h.beta0_given != rs.beta0_given))
+      bad = "hist_cap / T / beta0_given (records of different solves)";
+    if (!bad && h.T < 1) bad = "T";
+    if (bad) {
+      snprintf(msg, sizeof msg, "state record %d does not match the plan / parameters: %s",
+               idx[i], bad);
+      return fail(BSGP_ERR_ARG, msg);
+    }
+    if (prm->MAXIT <= h.iters_done) {
+      snprintf(msg, sizeof msg, "MAXIT = %d must exceed the %d iterations record %d has done",
+               prm->MAXIT, h.iters_done, idx[i]);
+      return fail(BSGP_ERR_ARG, msg);
+    }
+    if (i == 0) {
+      rs.sa.hist_cap = h.hist_cap;
+      rs.T = h.T;
+      rs.beta0_given = h.beta0_given;
+    }
+    if (!h.stopped) {
+      min_done = min_done < 0 ? h.iters_done : std::min(min_done, h.iters_done);
+      max_done = std::max(max_done, h.iters_done);
+    }
+  }
+  // the team size decides the order of every sum: it must be the records'
+  const int Tres = choose_team(p, B, prm->team == 0 ? rs.T : prm->team);
+  if (Tres != rs.T) {
+    snprintf(msg, sizeof msg,
+             "team: the records were solved with %d workgroups per image, this resume would "
+             "run %d",
+             rs.T, Tres);
+    return fail(BSGP_ERR_ARG, msg);
+  }
+  if (min_done < 0) min_done = max_done = prm->MAXIT;  // every record is stopped: nothing runs
+  rs.it0 = min_done + 1;
+  rs.uniform = min_done == max_done;
+  rs.done_it = min_done;
+  StateArgs& a = rs.sa;
+  a.rec = static_cast<unsigned char*>(const_cast<void*>(state_dev));
+  a.rec_bytes = (size_t)bytes_per_image;
+  a.index = index;
+  a.N = (int)N;
+  a.H = p->g.H;
+  a.W = p->g.W;
+  a.storage = p->storage;
+  a.conv_mode = p->conv_mode;
+  a.bmap = prm->bkg_is_map != 0;
+  a.L = state_layout(N, p->storage, a.bmap != 0, a.hist_cap);
+  a.beta0_given = rs.beta0_given;
+  return solve_impl(p, B, prm, nullptr, out, stream, nullptr, &rs);
 }
 
 int bsgp_apply_operator(bsgp_plan p, int32_t B, int32_t transpose, const double* x, double* out,

@@ -138,6 +138,60 @@ hipError_t persist_resident_per_cu(const SolveArgs& a, int K, size_t lds, int* p
 hipError_t persist_phase_prof(unsigned long long* out, int n, int reset);
 void persist_kernels_all(std::vector<const void*>& f);
 
+// ---- solver state records (bsgp_state.hip; layout in include/bsgp.h) -------
+static_assert(sizeof(bsgp_state_header) <= BSGP_STATE_HEADER_BYTES, "state header overflows");
+
+// Byte offsets of a record's sections (bsgp_state_layout's offs[]).
+struct StateLayout {
+  size_t bytes, discr, crit, times, flags, x, g, xtf, pw, gn, bkg;
+};
+inline size_t state_pad16(size_t v) { return (v + 15) / 16 * 16; }
+inline StateLayout state_layout(size_t N, int storage, bool bmap, int hist_cap) {
+  const size_t vb = storage == BSGP_STORAGE_F32 ? 4 : 8;
+  StateLayout L{};
+  size_t o = BSGP_STATE_HEADER_BYTES;
+  auto take = [&](size_t n) {
+    const size_t at = o;
+    o += state_pad16(n);
+    return at;
+  };
+  L.discr = take((size_t)hist_cap * 8);
+  L.crit = take((size_t)hist_cap * 8);
+  L.times = take((size_t)hist_cap * 8);
+  L.flags = take((size_t)hist_cap * 4);
+  L.x = take(N * vb);
+  L.g = take(N * vb);
+  L.xtf = take(N * vb);
+  L.pw = take(N * vb);
+  L.gn = take(N * 8);
+  L.bkg = bmap ? take(N * 8) : 0;
+  L.bytes = o;
+  return L;
+}
+
+// Arguments of k_state_save / k_state_load (by value: scalar loads).
+struct StateArgs {
+  unsigned char* rec;   // [B or n_state] records
+  size_t rec_bytes;     // bytes per record
+  const int* index;     // load: record of image i (nullptr: record i)
+  StateLayout L;
+  double* ws;           // the plan's slots (SolveArgs::ws / slot_stride / vec_stride)
+  size_t slot_stride, vec_stride;
+  ImgState* st;
+  int N, storage, bmap, hist_cap, T, conv_mode, H, W, beta0_given;
+  int M1;               // rows of the out arrays (MAXIT + 1 of the solve they belong to)
+  bsgp_outputs out;     // save: the finished solve's outputs; load: the resumed solve's
+  bsgp_params prm;      // save: the finished solve's parameters
+  int* active;          // load: counts the images that go on
+};
+hipError_t launch_state_save(const StateArgs& a, int B, hipStream_t s);
+hipError_t launch_state_load(const StateArgs& a, int B, hipStream_t s);
+// after k_state_load: seeds the persistent solver's slot order at iteration
+// `done_it` (queue == nullptr: no seeding) and, when no image goes on, tells the
+// host's lookahead poll so (done_host = seq)
+hipError_t launch_state_post(const StateArgs& a, int B, unsigned* queue, unsigned* done,
+                             int done_it, int* done_host, int seq, hipStream_t s);
+
 // Cooperative plans (Geo::coop) run the phase kernels of bsgp_solver_c512.hip:
 // the same kernels with 512-thread workgroups (two waves per SIMD per
 // workgroup where a long transform's LDS allows one or two workgroups per CU).

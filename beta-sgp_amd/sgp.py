@@ -552,11 +552,14 @@ def _solve_batch(variant, gns, psf, bkgs, betaParams=None, flux=None, init_recon
                  lr_exp_param=0.1, schedule_lr=False, ls_spec=None, ls_series=None,
                  streams=None, team=None, proj_cache=None, gn_compact=None,
                  device_out=False, profile=False, storage="f64", gn_f32=None, save=False,
-                 errflag=False, obj=None, persistent=None):
+                 errflag=False, obj=None, persistent=None, return_state=False):
     torch = _B.torch
     if save or errflag:  # sgp()/sgp_betaDiv() keywords: per-image files / err arrays
         raise ValueError("save / errflag are single-image options: use sgp / sgp_betaDiv")
     per_image = (psf.dim() if torch.is_tensor(psf) else np.ndim(psf)) == 3
+    if return_state and per_image:
+        raise ValueError("return_state=True needs one shared PSF: a solver state of per-image "
+                         "PSFs is not supported")
     _B.require_gpu()
     if not per_image:  # a shared PSF is checked in its own dtype before any upload
         psf = np.asarray(psf.cpu().numpy() if torch.is_tensor(psf) else psf)
@@ -609,6 +612,7 @@ def _solve_batch(variant, gns, psf, bkgs, betaParams=None, flux=None, init_recon
         fl = flux.to(device="cuda", dtype=torch.float64).reshape(-1).expand(Bn).contiguous()
     else:
         fl = _B.to_dev(np.broadcast_to(np.asarray(flux, dtype=np.float64), (Bn,)))
+    state = None
     if per_image:  # psf [B, kh, kw]: image i uses psf[i] (each checked as sgp.py:97-102)
         if len(psf) != Bn:
             raise ValueError("one PSF per image: psf must be [B, kh, kw]")
@@ -617,14 +621,88 @@ def _solve_batch(variant, gns, psf, bkgs, betaParams=None, flux=None, init_recon
     else:
         with _B.lease_plan(H, W, psf, mode, storage=storage) as plan:
             out = plan.solve(gns, bkgs, prm, flux=fl, x0=x0, beta0=b0, profile=profile)
+            # the state leaves the plan before the lease ends: the next solve
+            # on the plan overwrites its slots
+            state = _B.SolverState(plan.save_state(Bn), psf) if return_state else None
+    return _finish_batch(out, state, device_out)
+
+
+def _finish_batch(out, state, device_out):
+    """Device outputs of a batched solve as the batch functions return them."""
+    torch = _B.torch
     if device_out:
+        if state is not None:
+            out["state"] = state
         return out
     prof = {k: out.pop(k) for k in ("kernel_ms", "launches") if k in out}
     torch.cuda.current_stream().synchronize()
     _B.check_status(out["counters"])
     res = {k: (v.cpu().numpy() if v is not None else None) for k, v in out.items()}
     res.update(prof)
+    if state is not None:
+        res["state"] = state
     return res
+
+
+SolverState = _B.SolverState
+
+
+def state_params(variant, **kw):
+    """The ``Params`` of a batched solve with these keyword arguments (those of
+    ``sgp_batch`` / ``sgp_betaDiv_batch``, with their defaults), for
+    ``SolverState.from_arrays``.  ``variant``: 'kl' or 'beta'."""
+    d = dict(init_recon=0, proj_type=0, stop_criterion=0, MAXIT=500, gamma=1e-4, beta=0.4,
+             alpha=1.3, alpha_min=1e-5, alpha_max=1e5, M_alpha=3, tau=0.5, M=1, max_projs=1000,
+             verbose=True, ccd_sat_level=None, scale_data=True, tol_convergence=1e-4)
+    d.update({k: kw.pop(k) for k in list(kw) if k in d})
+    code = {"kl": _B.BSGP_VARIANT_KL, "beta": _B.BSGP_VARIANT_BETA}[variant]
+    return _params(code, **d, **kw)
+
+
+_RESUME_TUNING =("streams", "persistent", "proj_cache", "ls_spec", "team")
+
+
+def sgp_resume(state, MAXIT, images=None, device_out=False, return_state=False, **tuning):
+    """Continue a batched solve from a :class:`SolverState` (``out["state"]`` of
+    ``sgp_batch`` / ``sgp_betaDiv_batch(..., return_state=True)``, or
+    ``SolverState.load(path)``) up to ``MAXIT`` iterations in all.  Returns the
+    dict of the batch functions for the continued images, bit for bit what the
+    unsplit solve returns (``times`` excepted): complete history rows, and
+    images that had already stopped unchanged.  ``images`` is an index array:
+    a subset or a permutation of the saved images.  ``tuning`` accepts only
+    ``streams``, ``persistent``, ``proj_cache``, ``ls_spec`` (paths that are
+    bit-identical) and ``team``, which must be the saved team size.
+    ``return_state=True`` adds the new state as ``out["state"]``."""
+    torch = _B.torch
+    bad = sorted(set(tuning) - set(_RESUME_TUNING))
+    if bad:
+        raise ValueError(f"sgp_resume: {bad} cannot change on a resume (only "
+                         f"{list(_RESUME_TUNING)} may be given)")
+    state.validate()
+    h = state.header
+    prm = state.params()
+    prm.MAXIT = int(MAXIT)
+    prm.team = int(h["T"][0])  # the saved team size, whatever the batch size now
+    for k, v in tuning.items():
+        if v is not None:
+            setattr(prm, k, int(v))
+    if prm.variant == _B.BSGP_VARIANT_BETA and prm.adapt_beta:
+        prm.ls_spec = 1
+    _B.require_gpu()
+    H, W = state.shape
+    dev = state.to_device()
+    index = None
+    if images is not None:
+        idx = np.atleast_1d(np.asarray(images)).astype(np.int64)
+        if idx.size < 1 or idx.min() < -len(state) or idx.max() >= len(state):
+            raise ValueError(f"images must index the {len(state)} saved images")
+        index = torch.from_numpy((idx % len(state)).astype(np.int32)).to("cuda")
+    storage = int(h["storage"][0])
+    with _B.lease_plan(H, W, state.psf, int(h["conv_mode"][0]), storage=storage) as plan:
+        out = plan.resume(dev.records, prm, index=index)
+        new = (_B.SolverState(plan.save_state(out["iters"].numel()), state.psf)
+               if return_state else None)
+    return _finish_batch(out, new, device_out)
 
 
 def on_devices(devices, n, work):
@@ -693,6 +771,12 @@ def _solve_sharded(variant, gns, psf, bkgs, devices, betaParams=None, flux=None,
             for k in parts[0]}
 
 
+def _no_sharded_state(kw):
+    if kw.get("return_state"):
+        raise ValueError("return_state=True is not available with devices=[...]: a solver "
+                         "state sharded over GPUs is not supported")
+
+
 def sgp_batch(gns, psf, bkgs, devices=None, **kw):
     """KL-SGP on a batch [B, H, W] (one launch); psf is one [kh, kw] PSF or
     [B, kh, kw] (a PSF per image).  Returns a dict of arrays:
@@ -703,6 +787,7 @@ def sgp_batch(gns, psf, bkgs, devices=None, **kw):
     and scalar stays float64; SURVEY config C4); the default 'f64' is the
     reference's arithmetic."""
     if devices is not None:
+        _no_sharded_state(kw)
         return _solve_sharded(_B.BSGP_VARIANT_KL, gns, psf, bkgs, devices, **kw)
     return _solve_batch(_B.BSGP_VARIANT_KL, gns, psf, bkgs, **kw)
 
@@ -713,6 +798,7 @@ def sgp_betaDiv_batch(gns, psf, bkgs, betaParams=None, devices=None, **kw):
     launch).  Returns the dict of :func:`sgp_batch` plus beta_final [B].
     ``devices`` shards (image, beta) pairs over GPUs as in :func:`sgp_batch`."""
     if devices is not None:
+        _no_sharded_state(kw)
         return _solve_sharded(_B.BSGP_VARIANT_BETA, gns, psf, bkgs, devices,
                               betaParams=betaParams, **kw)
     return _solve_batch(_B.BSGP_VARIANT_BETA, gns, psf, bkgs, betaParams=betaParams, **kw)

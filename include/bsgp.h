@@ -287,6 +287,91 @@ int bsgp_psf_stamps(const bsgp_psf_model* model, const double* xy, int32_t n, in
  * subdivision).  Synchronous. */
 int bsgp_plan_set_psfs(bsgp_plan plan, const double* psfs_dev, int32_t n, void* stream);
 
+/* ---- solver state: save after a solve, resume later --------- */
+
+/* One fixed-size record per image, self-contained: a resume needs a plan of
+ * the same geometry and storage, the parameters and the records, not the
+ * original inputs.  A record is BSGP_STATE_HEADER_BYTES of header (the struct
+ * below, zero padded) followed by the sections of bsgp_state_layout, every
+ * section starting on a 16-byte boundary and zero padded to the next:
+ *   discr, crit, times  float64[hist_cap]   the outputs' rows 0..iters_done
+ *   flags               int32[hist_cap]
+ *   x, g, x_tf, pw      V[N], N = H*W, V = the plan's storage type: the iterate
+ *                       after iteration iters_done, its gradient, A(x) and
+ *                       den^(beta-1) (beta objective; unused for KL).  An image
+ *                       that a stop rule stopped holds the iterate it returned
+ *                       (sgp.py:424-438: the one before its last iteration).
+ *   gn                  float64[N]: the slot's scaled observed image verbatim
+ *                       (g32 != 0: the raw float32 values in its first half)
+ *   bkg                 float64[N] scaled background map (bkg_is_map only)
+ * The direction transform d_tf, the spectrum, the projection pixel lists and
+ * the team partials are rebuilt by every iteration and are not stored. */
+#define BSGP_STATE_MAGIC 0x53475342u /* "BSGS" */
+#define BSGP_STATE_VERSION 1
+#define BSGP_STATE_HEADER_BYTES 1024
+
+typedef struct {
+  uint32_t magic;        /* BSGP_STATE_MAGIC                                       */
+  uint32_t version;      /* BSGP_STATE_VERSION (layout version)                    */
+  int32_t H, W;
+  int32_t storage;       /* BSGP_STORAGE_*                                         */
+  int32_t conv_mode;     /* BSGP_CONV_*                                            */
+  int32_t hist_cap;      /* rows of the history sections (> iters_done)            */
+  int32_t T;             /* team size of the solve (counters[:, 5])                */
+  int32_t iters_done;    /* iterations completed                                   */
+  int32_t stopped;       /* 0: goes on when resumed (it ran out of MAXIT only);
+                            1: a stop rule (or a timeout, status bit 4) ended it;
+                            8: the setup ended it (status bit 8)                   */
+  int32_t Xones;         /* scaling matrix still ones (init_recon 0, no iteration) */
+  int32_t epoch;         /* lr_schedule's epoch (sgp.py:766-767)                   */
+  int32_t g32;           /* compact gn: 0 float64, 1 raw float32, 2 raw / scaling  */
+  int32_t beta0_given;   /* the solve had per-image betas (in->beta0)              */
+  int64_t record_bytes;  /* bytes of this record (bsgp_state_layout offs[0])       */
+  int64_t counters[7];   /* cumulative: E_p, E_ls, line-search passes, status bits,
+                            series trials, projection passes, list entries read    */
+  double scaling, flux, bkg_scalar; /* scaled flux; scaled scalar background       */
+  double x_low, x_upp;   /* scaling-matrix bounds (sgp.py:268-273)                 */
+  double Dcoeff, tol;    /* 2/N*scaling; the stop rule's tolerance                 */
+  double elapsed;        /* seconds of solve time so far (times continue from it)  */
+  double fv, alpha, tau, lr, init_lr, beta;
+  double lam_p, lam_ratio, kappa; /* projection multiplier history (proj_cache)    */
+  double konst;          /* lambda-independent objective sum at `beta`             */
+  double gfill;          /* null-pixel fill of a compact gn                        */
+  double Valpha[32];     /* first M_alpha entries used                             */
+  double Fold[32];       /* first M entries used                                   */
+  bsgp_params prm;       /* the parameters of the solve (validated on resume)      */
+} bsgp_state_header;
+
+/* Byte offsets inside a record for a geometry (no plan, no device needed):
+ * offs[0] = record bytes, then the offsets of discr, crit, times, flags, x, g,
+ * x_tf, pw, gn, bkg (offs[10] = 0 without a background map). */
+int bsgp_state_layout(int32_t H, int32_t W, int32_t storage, int32_t bkg_is_map,
+                      int32_t hist_cap, int64_t* offs /* [11] */);
+/* Record bytes for a plan and a history of MAXIT_done_max + 1 rows. */
+int bsgp_state_bytes(bsgp_plan plan, int32_t bkg_is_map, int32_t MAXIT_done_max,
+                     int64_t* bytes_per_image);
+/* Gather the state the last bsgp_solve_device / bsgp_solve_resume on this plan
+ * left in its workspace into state_dev: B records of bytes_per_image =
+ * bsgp_state_bytes(plan, bkg_is_map, MAXIT) each.  B is that solve's B; its
+ * output buffers must still be valid (their discr / crit / times / flags rows
+ * are the history; stop rule 2 needs out->crit), and no other solve may have
+ * run on the plan in between.  Asynchronous. */
+int bsgp_state_save(bsgp_plan plan, int32_t B, void* state_dev, int64_t bytes_per_image,
+                    void* stream);
+/* Continue B images from records up to params->MAXIT.  state_dev holds n_state
+ * records of bytes_per_image; image i of this solve is record index[i] (device
+ * int32 [B]) or record i (index NULL, B <= n_state).  The plan's geometry, mode
+ * and storage, the team size and every numerical parameter must be the
+ * record's (BSGP_ERR_ARG names the field that differs); MAXIT must exceed the
+ * iterations done; streams, persistent, proj_cache and ls_spec may differ.
+ * Outputs are those of the unsplit solve, bit for bit (times excepted), with
+ * complete history rows; images whose record is stopped keep their results.
+ * out->err / out->x_iter: BSGP_ERR_UNSUPPORTED.  Reads the record headers on
+ * the host first (one stream synchronisation), then asynchronous. */
+int bsgp_solve_resume(bsgp_plan plan, int32_t B, const bsgp_params* params,
+                      const void* state_dev, int32_t n_state, int64_t bytes_per_image,
+                      const int32_t* index, const bsgp_outputs* out, void* stream);
+
 int bsgp_device_synchronize(void);
 const char* bsgp_last_error(void);
 int32_t bsgp_abi_version(void);
