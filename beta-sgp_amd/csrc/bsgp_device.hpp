@@ -15,6 +15,7 @@
 #include <type_traits>
 
 #include "bsgp_fft.hpp"
+#include "bsgp_lanesplit.hpp"
 #include "bsgp_math.hpp"
 
 namespace bsgp {
@@ -897,6 +898,68 @@ __device__ __forceinline__ void load_rows(LD& ld, int r, bool two, int j0, int l
   }
 }
 
+// Wide operand loads (bsgp_lanesplit.hpp): on even-width images a lane loads
+// two adjacent pixels of ONE row, 16 B of float64 per array instead of 8 B,
+// in half the memory instructions; `ld2(r, j) -> Two<V>` loads the operands of
+// pixels (r, j) and (r, j + 1), j even.  A pass without one passes NoWide.
+// The direction's rows and k_bb's have one (C3, same box: +0.3 % and +0.2 %);
+// the line search's two row passes lost 0.6 % and 0.4 % with theirs at their
+// 168-VGPR budget, and wide stores (a second swap of what the consumer
+// returns) lost in every pass, so those keep one pixel per lane.
+template <class V>
+struct Two {
+  V a, b;
+};
+struct NoWide {};
+
+// Swap the upper half-wave of `a` with the lower half-wave of `b`, dword by
+// dword (v_permlane32_swap).  Every lane of the wave must be active.
+template <class T>
+__device__ __forceinline__ void half_swap(T& a, T& b) {
+  static_assert(sizeof(T) % 4 == 0, "whole dwords");
+  constexpr int N = sizeof(T) / 4;
+  unsigned int x[N], y[N];
+  __builtin_memcpy(x, &a, sizeof(T));
+  __builtin_memcpy(y, &b, sizeof(T));
+#pragma unroll
+  for (int n = 0; n < N; ++n) {
+    const auto s = __builtin_amdgcn_permlane32_swap(x[n], y[n], false, false);
+    x[n] = s[0];
+    y[n] = s[1];
+  }
+  __builtin_memcpy(&a, x, sizeof(T));
+  __builtin_memcpy(&b, y, sizeof(T));
+}
+
+// Whether the per-wave row passes of this plan load wide where they have a
+// wide loader (the condition row_fwd2 / row_inv2 test; wave-uniform)
+template <bool COOP>
+__device__ __forceinline__ bool row_wide(const Geo& G) {
+  return !COOP && (G.W & 1) == 0;
+}
+
+// The value lane L held in the one-pixel scheme, from the wide scheme's lanes:
+// per-lane partial sums go back to their lanes before a reduction, so its
+// tree adds the same pairs in the same order.
+__device__ __forceinline__ double split_undo(double v) {
+  return __shfl(v, split_lane((int)(threadIdx.x & 63u)), 64);
+}
+
+// load_rows for the wide scheme: one load per lane and 64-column chunk; the
+// swap happens where the batch is consumed (half_swap), so the loads stay in
+// flight until then.  Branch-free like load_rows.
+template <int JCH, class LD2, class V>
+__device__ __forceinline__ void load_rows2(LD2& ld2, int r, bool two, int j0, int lane, int ncols,
+                                           V (&v0)[JCH], V (&v1)[JCH]) {
+  const int rr = (two && split_half(lane)) ? r + 1 : r;
+#pragma unroll
+  for (int u = 0; u < JCH; ++u) {
+    const Two<V> q = ld2(rr, split_pair_clamped(j0 + 64 * u, lane, ncols));
+    v0[u] = q.a;
+    v1[u] = q.b;
+  }
+}
+
 // ---------------------------------------------------- cooperative passes
 // Geo::coop: transforms too long for one wave's share of the LDS (the 2048-point
 // rows and columns of config C4, the 400/480-point grids of the application's
@@ -1443,10 +1506,13 @@ __device__ __forceinline__ void coop_col_conv(const Geo& G, const Part& D, cd* s
 // PIPE: the operand batch j0 + 64*JCH is issued before batch j0 is computed
 // (two batches in flight per wave instead of one round trip per batch; costs
 // a second set of batch registers outside the FFT).
+// ld2: the pass's wide loader, if it has one (Two<V> above): rows of even
+// length take it, odd lengths and cooperative plans keep ld.
 template <int JCH = kJCH, bool PF = false, bool COMP = true, bool COOP = false,
-          bool PIPE = false, int PHS = -1, class LD, class MK>
+          bool PIPE = false, int PHS = -1, class LD, class MK, class LD2 = NoWide>
 __device__ __forceinline__ void row_fwd2(const Geo& G, const Part& D, int nrows, int ncols,
-                                         int ldim, cd* spec, cd* lds, LD&& ld, MK&& mk) {
+                                         int ldim, cd* spec, cd* lds, LD&& ld, MK&& mk,
+                                         LD2&& ld2 = LD2{}) {
   if constexpr (COOP) {
     coop_row_fwd(G, D, nrows, ncols, ldim, spec, lds, ld, mk);
     return;
@@ -1454,24 +1520,38 @@ __device__ __forceinline__ void row_fwd2(const Geo& G, const Part& D, int nrows,
   using V = decltype(ld(0, 0));
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const bool pair_ok = (ldim & 1) == 0;
+  constexpr bool kHasWide =
+      !std::is_same<typename std::decay<LD2>::type, NoWide>::value;
   if (w < G.nfw) {
+    // (the loader is an argument so that the wide branch depends on the
+    // generic lambda's parameters and is not instantiated for NoWide)
+    auto run = [&](auto wide_c, auto& ldw) __attribute__((always_inline)) {
+    constexpr bool WIDE = decltype(wide_c)::value;
+    auto load = [&](int rr, bool two_r, int j0, V (&w0)[JCH], V (&w1)[JCH]) __attribute__((always_inline)) {
+      if constexpr (WIDE)
+        load_rows2<JCH>(ldw, rr, two_r, j0, lane, ncols, w0, w1);
+      else
+        load_rows<JCH>(ld, rr, two_r, j0, lane, ncols, w0, w1);
+    };
     cd* a = lds + w * 2 * G.lpad;
     cd* b = a + G.lpad;
     int r = 2 * (D.gw0 + w);
     V v0[JCH], v1[JCH];
-    if (PF && r < nrows) load_rows<JCH>(ld, r, (r + 1) < nrows, 0, lane, ncols, v0, v1);
+    if (PF && r < nrows) load(r, (r + 1) < nrows, 0, v0, v1);
     PH_SUB_T(tph);
     for (; r < nrows; r += 2 * D.gws) {
       const bool two = (r + 1) < nrows;
       auto put = [&](int j0, const V (&w0)[JCH], const V (&w1)[JCH]) __attribute__((always_inline)) {
 #pragma unroll
         for (int u = 0; u < JCH; ++u) {
-          const int j = j0 + lane + 64 * u;
+          V q0 = w0[u], q1 = w1[u];
+          if constexpr (WIDE) half_swap(q0, q1);  // one column of both rows
+          const int j = j0 + 64 * u + (WIDE ? split_col(lane) : lane);
           if (j < G.Q) {
             double va = 0.0, vb = 0.0;
             if (j < ncols) {
-              va = mk(r, j, w0[u]);
-              if (two) vb = mk(r + 1, j, w1[u]);
+              va = mk(r, j, q0);
+              if (two) vb = mk(r + 1, j, q1);
             }
             a[j] = cmk(va, vb);
           }
@@ -1480,15 +1560,15 @@ __device__ __forceinline__ void row_fwd2(const Geo& G, const Part& D, int nrows,
       if constexpr (PIPE) {
         constexpr int S = 64 * JCH;
         V u0[JCH], u1[JCH];
-        if (!PF) load_rows<JCH>(ld, r, two, 0, lane, ncols, v0, v1);
+        if (!PF) load(r, two, 0, v0, v1);
         // (loads past the row end are clamped, not skipped: a skipped load
         // would be a branch whose join waits for every load in flight)
         for (int j0 = 0; j0 < G.Q; j0 += 2 * S) {
           // (no loads for batches wholly in the zero padding, j >= ncols)
-          if (j0 + S < ncols) load_rows<JCH>(ld, r, two, j0 + S, lane, ncols, u0, u1);
+          if (j0 + S < ncols) load(r, two, j0 + S, u0, u1);
           put(j0, v0, v1);
           if (j0 + S < G.Q) {
-            if (j0 + 2 * S < ncols) load_rows<JCH>(ld, r, two, j0 + 2 * S, lane, ncols, v0, v1);
+            if (j0 + 2 * S < ncols) load(r, two, j0 + 2 * S, v0, v1);
             put(j0 + S, u0, u1);
           }
         }
@@ -1496,12 +1576,12 @@ __device__ __forceinline__ void row_fwd2(const Geo& G, const Part& D, int nrows,
         for (int j0 = 0; j0 < G.Q; j0 += 64 * JCH) {
           // batches wholly in the zero padding (j0 >= ncols: the 256..269 of a
           // 270-point row) load nothing: put() writes zeros there
-          if ((!PF || j0 > 0) && j0 < ncols) load_rows<JCH>(ld, r, two, j0, lane, ncols, v0, v1);
+          if ((!PF || j0 > 0) && j0 < ncols) load(r, two, j0, v0, v1);
           put(j0, v0, v1);
         }
       }
       const int rn = r + 2 * D.gws;
-      if (PF && rn < nrows) load_rows<JCH>(ld, rn, (rn + 1) < nrows, 0, lane, ncols, v0, v1);
+      if (PF && rn < nrows) load(rn, (rn + 1) < nrows, 0, v0, v1);
       wave_sync();
       PH_SUB(PHS, tph);
       cd* Z = fft_any<COMP>(a, b, G.fq, false, lane, 64, WaveSync());
@@ -1513,6 +1593,15 @@ __device__ __forceinline__ void row_fwd2(const Geo& G, const Part& D, int nrows,
       }
       wave_sync();
       PH_SUB(PHS + 2, tph);
+    }
+    };
+    if constexpr (kHasWide) {
+      if ((ncols & 1) == 0)
+        run(std::true_type{}, ld2);
+      else
+        run(std::false_type{}, ld2);
+    } else {
+      run(std::false_type{}, ld2);
     }
   }
 }
@@ -1550,29 +1639,29 @@ __device__ __forceinline__ void gather_pair(const Geo& G, const cd* spec, int ld
   }
 }
 
-// LDS-DMA staging of one row pair's stored spectrum: F[k] = spec[k][r] and
-// F[Qh + k] = spec[k][r + 1] for k < Qh (global_load_lds_dwordx4: the LDS
-// destination is the wave-uniform base + 16 B * lane).  Needs lpad >= 2*Qh.
+// LDS-DMA staging of one row pair's stored spectrum: F[2k] = spec[k][r] and
+// F[2k + 1] = spec[k][r + 1] for k < Qh (global_load_lds_dwordx4: the LDS
+// destination is the wave-uniform base + 16 B * lane).  Lanes 2i and 2i + 1
+// fetch the two 16-B halves of column k0 + i, 32 contiguous bytes, so one
+// instruction touches 32 cache lines; a lane per column and one instruction
+// per row touched 64 and asked for every line twice.  Needs lpad >= 2*Qh.
 typedef __attribute__((address_space(3))) void lds_void_t;
 typedef __attribute__((address_space(1))) void gbl_void_t;
 __device__ __forceinline__ void stage_pair(const Geo& G, const cd* spec, int ld, int r, bool two,
                                            cd* F, int lane) {
-  for (int k0 = 0; k0 < G.Qh; k0 += 64) {
-    const int k = k0 + lane;
-    if (k < G.Qh) {
-      const cd* col = spec + (size_t)k * ld + r;
-      __builtin_amdgcn_global_load_lds((gbl_void_t*)col, (lds_void_t*)(F + k0), 16, 0, 0);
-      if (two)
-        __builtin_amdgcn_global_load_lds((gbl_void_t*)(col + 1), (lds_void_t*)(F + G.Qh + k0), 16,
-                                         0, 0);
+  for (int k0 = 0; k0 < G.Qh; k0 += 32) {
+    const int k = k0 + (lane >> 1);
+    if (k < G.Qh) {  // (without a row r + 1 the odd lanes fetch row r again, unused)
+      const cd* col = spec + (size_t)k * ld + r + (two ? (lane & 1) : 0);
+      __builtin_amdgcn_global_load_lds((gbl_void_t*)col, (lds_void_t*)(F + 2 * k0), 16, 0, 0);
     }
   }
 }
 // Full-length spectrum of the staged pair into `a` (as gather_pair).
 __device__ __forceinline__ void unpack_pair(const Geo& G, const cd* F, bool two, cd* a, int lane) {
   for (int k = lane; k < G.Qh; k += 64) {
-    const cd A = F[k];
-    const cd B = two ? F[G.Qh + k] : cmk(0.0, 0.0);
+    const cd A = F[2 * k];
+    const cd B = two ? F[2 * k + 1] : cmk(0.0, 0.0);
     a[k] = cmk(A.x - B.y, A.y + B.x);
     if (k > 0 && G.Q - k >= G.Qh) a[G.Q - k] = cmk(A.x + B.y, B.x - A.y);
   }
@@ -1587,17 +1676,28 @@ __device__ __forceinline__ void unpack_pair(const Geo& G, const cd* F, bool two,
 // PRE: the first operand batch is issued before the FFT (costs its registers
 // across the FFT).
 // PIPE: as row_fwd2 (batch j0 + 64*JCH in flight while batch j0 is consumed).
+// ld2: as row_fwd2.
 template <bool PRE, int JCH = kJCH, bool COMP = true, bool COOP = false,
-          bool PIPE = false, int PHS = -1, class LD, class USE>
+          bool PIPE = false, int PHS = -1, class LD, class USE, class LD2 = NoWide>
 __device__ __forceinline__ void row_inv2(const Geo& G, const Part& D, const cd* spec, cd* lds,
-                                         LD&& ld, USE&& use) {
+                                         LD&& ld, USE&& use, LD2&& ld2 = LD2{}) {
   if constexpr (COOP) {
     coop_row_inv(G, D, spec, lds, ld, use);
     return;
   }
   using V = decltype(ld(0, 0));
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  constexpr bool kHasWide =
+      !std::is_same<typename std::decay<LD2>::type, NoWide>::value;
   if (w < G.nfw) {
+    auto run = [&](auto wide_c, auto& ldw) __attribute__((always_inline)) {  // (as row_fwd2)
+    constexpr bool WIDE = decltype(wide_c)::value;
+    auto load = [&](int rr, bool two_r, int j0, V (&w0)[JCH], V (&w1)[JCH]) __attribute__((always_inline)) {
+      if constexpr (WIDE)
+        load_rows2<JCH>(ldw, rr, two_r, j0, lane, G.W, w0, w1);
+      else
+        load_rows<JCH>(ld, rr, two_r, j0, lane, G.W, w0, w1);
+    };
     cd* in = lds + w * 2 * G.lpad;
     cd* other = in + G.lpad;
     int r = 2 * (D.gw0 + w);
@@ -1606,7 +1706,7 @@ __device__ __forceinline__ void row_inv2(const Geo& G, const Part& D, const cd* 
     for (; r < G.H; r += 2 * D.gws) {
       const bool two = (r + 1) < G.H;
       V v0[JCH], v1[JCH];
-      if (PRE) load_rows<JCH>(ld, r, two, 0, lane, G.W, v0, v1);
+      if (PRE) load(r, two, 0, v0, v1);
       wave_sync();
       PH_SUB(PHS + 2, tph);
       cd* Z = fft_any<COMP>(in, other, G.fq, true, lane, 64, WaveSync());
@@ -1618,29 +1718,31 @@ __device__ __forceinline__ void row_inv2(const Geo& G, const Part& D, const cd* 
       auto eat = [&](int j0, const V (&w0)[JCH], const V (&w1)[JCH]) __attribute__((always_inline)) {
 #pragma unroll
         for (int u = 0; u < JCH; ++u) {
-          const int j = j0 + lane + 64 * u;
+          V q0 = w0[u], q1 = w1[u];
+          if constexpr (WIDE) half_swap(q0, q1);  // one column of both rows
+          const int j = j0 + 64 * u + (WIDE ? split_col(lane) : lane);
           if (j < G.W) {
             const cd z = Z[j];
-            use(r, j, z.x, w0[u]);
-            if (two) use(r + 1, j, z.y, w1[u]);
+            use(r, j, z.x, q0);
+            if (two) use(r + 1, j, z.y, q1);
           }
         }
       };
       if constexpr (PIPE) {
         constexpr int S = 64 * JCH;
         V u0[JCH], u1[JCH];
-        if (!PRE) load_rows<JCH>(ld, r, two, 0, lane, G.W, v0, v1);
+        if (!PRE) load(r, two, 0, v0, v1);
         for (int j0 = 0; j0 < G.W; j0 += 2 * S) {
-          load_rows<JCH>(ld, r, two, j0 + S, lane, G.W, u0, u1);  // clamped (see row_fwd2)
+          load(r, two, j0 + S, u0, u1);  // clamped (see row_fwd2)
           eat(j0, v0, v1);
           if (j0 + S < G.W) {
-            load_rows<JCH>(ld, r, two, j0 + 2 * S, lane, G.W, v0, v1);
+            load(r, two, j0 + 2 * S, v0, v1);
             eat(j0 + S, u0, u1);
           }
         }
       } else {
         for (int j0 = 0; j0 < G.W; j0 += 64 * JCH) {
-          if (!PRE || j0 > 0) load_rows<JCH>(ld, r, two, j0, lane, G.W, v0, v1);
+          if (!PRE || j0 > 0) load(r, two, j0, v0, v1);
           eat(j0, v0, v1);
         }
       }
@@ -1654,6 +1756,15 @@ __device__ __forceinline__ void row_inv2(const Geo& G, const Part& D, const cd* 
       }
     }
     wave_sync();
+    };
+    if constexpr (kHasWide) {
+      if ((G.W & 1) == 0)
+        run(std::true_type{}, ld2);
+      else
+        run(std::false_type{}, ld2);
+    } else {
+      run(std::false_type{}, ld2);
+    }
   }
 }
 

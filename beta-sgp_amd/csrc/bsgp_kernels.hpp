@@ -155,7 +155,8 @@ __device__ __forceinline__ double opt_ld(bool on, const T* a, int i, double off)
   const double v = (double)a[on ? i : 0];
   return on ? v : off;
 }
-__device__ __forceinline__ double2 opt_ld2(bool on, const double* a, int p, double off) {
+template <class T>
+__device__ __forceinline__ double2 opt_ld2(bool on, const T* a, int p, double off) {
   const double2 v = ld2(a, on ? p : 0);
   return on ? v : double2{off, off};
 }
@@ -1005,7 +1006,13 @@ __device__ __forceinline__ void dir_phase(const SolveArgs& A, int img) {
         const double d = D.d(v.x, v.y);
         gd[0] += d * v.y;
         return d;
+      },
+      [&](int r, int j) {
+        const int p = (r * G.W + j) >> 1;
+        const double2 x = ld2(B.xa, p), g = ld2(B.ga, p);
+        return Two<double2>{double2{x.x, g.x}, double2{x.y, g.y}};
       });
+  if (row_wide<COOP>(G)) gd[0] = split_undo(gd[0]);  // the partials back to their lanes
   team_sum<1>(gd, red, tm);
   PH_ADD(1, tk1);
   PH_ADD(2, tk0);
@@ -1585,7 +1592,16 @@ __device__ __forceinline__ void bb_phase(const SolveArgs& A, int img) {
     bb[5] += xn * xn;
     B.xb[i] = xn;
     B.gb[i] = gnew;
-  });
+  },
+      [&](int r, int j) {
+        const int p = (r * G.W + j) >> 1;
+        const double2 pw = opt_ld2(beta_obj, B.pw, p, 1.0), x = ld2(B.xa, p), g = ld2(B.ga, p);
+        return Two<BbIn>{BbIn{pw.x, x.x, g.x}, BbIn{pw.y, x.y, g.y}};
+      });
+  if (row_wide<COOP>(G)) {
+#pragma unroll
+    for (int k = 0; k < 6; ++k) bb[k] = split_undo(bb[k]);
+  }
   team_sum<6>(bb, red, tm);
   PH_ADD(8, tk0);
   // Barzilai-Borwein (sgp.py:366-386)
