@@ -32,6 +32,8 @@ BSGP_ERR_ARG = -1
 BSGP_ERR_HIP = -2
 BSGP_ERR_UNSUPPORTED = -3
 BSGP_ERR_PSF = -4
+BSGP_DTYPE_F32 = 0
+BSGP_DTYPE_F64 = 1
 
 
 class BsgpError(RuntimeError):
@@ -157,6 +159,8 @@ def lib():
             L.bsgp_state_bytes.argtypes = [vp, i32, i32, ctypes.POINTER(i64)]
             L.bsgp_state_save.argtypes = [vp, i32, vp, i64, vp]
             L.bsgp_solve_resume.argtypes = [vp, i32, vp, vp, i32, i64, vp, vp, vp]
+            L.bsgp_background2d.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, i32, dbl, i32,
+                                            dbl, i32, vp, vp, vp, vp, vp, vp, vp, vp]
             for name in ["bsgp_plan_create", "bsgp_plan_create_checked", "bsgp_plan_destroy", "bsgp_plan_info",
                          "bsgp_solve_device", "bsgp_solve_host", "bsgp_solve_profiled",
                          "bsgp_apply_operator",
@@ -164,7 +168,8 @@ def lib():
                          "bsgp_beta_div_grad_parts", "bsgp_device_synchronize",
                          "bsgp_extract_tiles", "bsgp_coadd_tiles", "bsgp_fits_to_f64",
                          "bsgp_psf_stamps", "bsgp_plan_set_psfs", "bsgp_state_layout",
-                         "bsgp_state_bytes", "bsgp_state_save", "bsgp_solve_resume"]:
+                         "bsgp_state_bytes", "bsgp_state_save", "bsgp_solve_resume",
+                         "bsgp_background2d"]:
                 getattr(L, name).restype = ctypes.c_int
             if L.bsgp_abi_version() != ABI_VERSION:
                 raise BsgpError(-3, f"{LIB_PATH} has ABI {L.bsgp_abi_version()}, this binding "
@@ -178,7 +183,7 @@ EXPORTED = ["bsgp_plan_create", "bsgp_plan_create_checked", "bsgp_plan_destroy",
             "bsgp_beta_div_deriv", "bsgp_beta_div_grad_parts", "bsgp_device_synchronize",
             "bsgp_last_error", "bsgp_abi_version", "bsgp_extract_tiles", "bsgp_coadd_tiles",
             "bsgp_fits_to_f64", "bsgp_psf_stamps", "bsgp_plan_set_psfs", "bsgp_state_layout",
-            "bsgp_state_bytes", "bsgp_state_save", "bsgp_solve_resume"]
+            "bsgp_state_bytes", "bsgp_state_save", "bsgp_solve_resume", "bsgp_background2d"]
 
 
 def check(rc):

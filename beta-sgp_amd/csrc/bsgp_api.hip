@@ -1484,6 +1484,68 @@ int bsgp_psf_stamps(const bsgp_psf_model* m, const double* xy, int32_t n, int32_
   return BSGP_OK;
 }
 
+int bsgp_background2d(const void* data, int32_t dtype, int32_t B, int32_t H, int32_t W, int32_t bh,
+                      int32_t bw, int32_t fh, int32_t fw, double sigma, int32_t maxiters,
+                      double exclude_percentile, int32_t clip, const uint8_t* mask, double* bkg_out,
+                      double* rms_out, double* mesh_out, double* rms_mesh_out, double* medians_out,
+                      int32_t* status_out, void* stream) {
+  if (!data) return fail(BSGP_ERR_ARG, "data is NULL");
+  if (dtype != BSGP_DTYPE_F32 && dtype != BSGP_DTYPE_F64)
+    return fail(BSGP_ERR_ARG, "dtype must be BSGP_DTYPE_F32 or BSGP_DTYPE_F64");
+  if (B < 1 || H < 1 || W < 1) return fail(BSGP_ERR_ARG, "B, H and W must be >= 1");
+  if (bh < 1 || bw < 1) return fail(BSGP_ERR_ARG, "box size (bh, bw) must be >= 1");
+  if (fh < 1 || fw < 1 || fh % 2 == 0 || fw % 2 == 0)
+    return fail(BSGP_ERR_ARG, "filter size (fh, fw) must be odd and >= 1");
+  if (!(sigma >= 0.0)) return fail(BSGP_ERR_ARG, "sigma must be >= 0");
+  if (maxiters < 0) return fail(BSGP_ERR_ARG, "maxiters must be >= 0");
+  if (!(exclude_percentile >= 0.0 && exclude_percentile <= 100.0))
+    return fail(BSGP_ERR_ARG, "exclude_percentile must be in [0, 100]");
+  char msg[192];
+  if ((int64_t)bh * bw > kBkgMaxBox) {
+    snprintf(msg, sizeof msg, "box of %lld pixels: a box holds at most %d (bh * bw <= %d)",
+             (long long)bh * bw, kBkgMaxBox, kBkgMaxBox);
+    return fail(BSGP_ERR_UNSUPPORTED, msg);
+  }
+  if (fh > kBkgMaxFilter || fw > kBkgMaxFilter) {
+    snprintf(msg, sizeof msg, "filter window larger than %d x %d", kBkgMaxFilter, kBkgMaxFilter);
+    return fail(BSGP_ERR_UNSUPPORTED, msg);
+  }
+  const int64_t ny = (H + (int64_t)bh - 1) / bh, nx = (W + (int64_t)bw - 1) / bw;
+  if (ny * nx > kBkgMaxCells) {
+    snprintf(msg, sizeof msg, "mesh of %lld cells: an image's mesh holds at most %d",
+             (long long)(ny * nx), kBkgMaxCells);
+    return fail(BSGP_ERR_UNSUPPORTED, msg);
+  }
+  if (B > 65535 || H > 65535)
+    return fail(BSGP_ERR_UNSUPPORTED, "B and H must be at most 65535");
+  const size_t ncell = (size_t)(ny * nx);
+  BkgArgs a{};
+  a.data = data;
+  a.mask = mask;
+  a.B = B, a.H = H, a.W = W, a.bh = bh, a.bw = bw, a.fh = fh, a.fw = fw;
+  a.ny = (int)ny, a.nx = (int)nx, a.maxiters = maxiters, a.clip = clip ? 1 : 0;
+  a.sigma = sigma;
+  a.excl_count = exclude_percentile / 100.0 * (double)(bh * bw);
+  a.ws_stride = 6 * ncell + 8;
+  a.bkg = bkg_out, a.rms = rms_out, a.mesh = mesh_out, a.rms_mesh = rms_mesh_out;
+  a.medians = medians_out, a.status = status_out;
+  hipStream_t s = (hipStream_t)stream;
+  // stream-ordered workspace: the call stays asynchronous
+  const size_t wsb = (size_t)B * a.ws_stride * sizeof(double);
+  const size_t wib = (size_t)B * (1 + 3 * ncell) * sizeof(int);
+  void* w = nullptr;
+  HIP_TRY(hipMallocAsync(&w, wsb + wib, s));
+  a.ws = static_cast<double*>(w);
+  a.wsi = reinterpret_cast<int*>(static_cast<char*>(w) + wsb);
+  hipError_t e = launch_bkg_boxstats(a, dtype == BSGP_DTYPE_F32, s);
+  if (e == hipSuccess) e = launch_bkg_mesh(a, s);
+  if (e == hipSuccess && (bkg_out || rms_out)) e = launch_bkg_zoom(a, s);
+  const hipError_t ef = hipFreeAsync(w, s);
+  if (e != hipSuccess) return fail(BSGP_ERR_HIP, std::string("background launch: ") + hipGetErrorString(e));
+  HIP_TRY(ef);
+  return BSGP_OK;
+}
+
 int bsgp_beta_div(int64_t n, const double* y, const double* x, double beta, double* out,
                   void* stream) {
   if (n < 1 || n > 0x7fffffff || !y || !x || !out) return fail(BSGP_ERR_ARG, "bad arguments");

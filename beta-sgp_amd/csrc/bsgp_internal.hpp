@@ -125,6 +125,29 @@ hipError_t launch_coadd_tiles(const double* tiles, int n, int th, int tw, const 
                               int W, double* mean, double* footprint, hipStream_t s);
 hipError_t launch_fits_to_f64(const void* raw, int64_t n, int bitpix, double bscale, double bzero,
                               double* out, hipStream_t s);
+// ---- sky background (bsgp_background.hip) ----------------------
+constexpr int kBkgMaxBox = 4096;    // pixels of one box: its sorted copy is 32 KiB of LDS
+constexpr int kBkgMaxCells = 4096;  // cells of one image's mesh (k_bkg_mesh keeps two copies in LDS)
+constexpr int kBkgMaxFilter = 7;    // median filter window, per axis
+constexpr int kBkgZoomLine = 520;   // k_bkg_zoom's folded coefficient line (512 pixels / bw + 4)
+// Arguments of the three background kernels (by value: scalar loads).
+struct BkgArgs {
+  const void* data;           // [B][H][W] float32 or float64
+  const unsigned char* mask;  // [B][H][W] bytes, nonzero = masked, or nullptr
+  int B, H, W, bh, bw, fh, fw, ny, nx, maxiters, clip;
+  double sigma;
+  double excl_count;  // a box with more invalid pixels than this is excluded
+  // per image: raw median / std meshes, filtered meshes, spline coefficients
+  // (2 x ny*nx each), then {min, max} of both filtered meshes and their medians
+  double* ws;
+  size_t ws_stride;  // doubles per image: 6 * ny*nx + 8
+  int* wsi;          // per image: kept cells, then excluded / survivors / iterations [ny*nx] each
+  double *bkg, *rms, *mesh, *rms_mesh, *medians;  // outputs, any may be nullptr
+  int* status;                                    // output copy of wsi, or nullptr
+};
+hipError_t launch_bkg_boxstats(const BkgArgs& a, int f32, hipStream_t s);
+hipError_t launch_bkg_mesh(const BkgArgs& a, hipStream_t s);
+hipError_t launch_bkg_zoom(const BkgArgs& a, hipStream_t s);
 struct PsfModel;
 hipError_t launch_psf_stamps(const PsfModel& m, const double* xy, int n, int spatial,
                              int normalize, double* out, hipStream_t s);

@@ -121,18 +121,34 @@ def _check_bkg_dtype(gn_f32, bkg):
                          "images one at a time with sgp_betaDiv / sgp)")
 
 
+def _estimate_bkg(image, bkg, box_size, filter_size):
+    """``bkg="estimate"``: the field's background map from background.Background2D
+    (utils.py:235-239), estimated once on the device in float64 and left
+    there; any other ``bkg`` is returned as it is."""
+    if not isinstance(bkg, str):
+        return bkg
+    if bkg != "estimate":
+        raise ValueError(f'bkg must be a scalar, a map or "estimate", got {bkg!r}')
+    if box_size is None:
+        raise ValueError('bkg="estimate" needs bkg_box_size (Background2D\'s box_size)')
+    from background import Background2D
+    return Background2D(image, box_size, filter_size=filter_size, device_out=True).background
+
+
 def sgp_subdivisions(image, psf, bkg, subdiv_shape=(256, 256), overlap=32, betaParams=None,
-                     device_out=False, **sgp_kwargs):
+                     device_out=False, bkg_box_size=None, bkg_filter_size=(3, 3), **sgp_kwargs):
     """Field -> overlapping subdivisions -> one batched beta-SGP solve -> mean
     mosaic.  ``bkg``: scalar, or a field-sized map (cut like the image, as the
     application cuts its background map).  ``psf``: one stamp for every tile,
     [n_tiles, kh, kw] stamps, or a DIAPL model (psf_calculate.PSF), which is
     evaluated on the device at every tile centre (field pixel coordinates,
     (x, y) = ((x0 + x1 - 1) / 2, (y0 + y1 - 1) / 2)) so each tile is solved
-    with its own PSF.  Returns (mosaic, footprint, solve outputs); numpy
-    unless device_out."""
+    with its own PSF.  ``bkg="estimate"`` estimates the map from the field
+    itself with background.Background2D(image, bkg_box_size, bkg_filter_size).
+    Returns (mosaic, footprint, solve outputs); numpy unless device_out."""
     import sgp
     torch = _B.torch
+    bkg = _estimate_bkg(image, bkg, bkg_box_size, bkg_filter_size)
     # a float32 field (the application's FITS data) keeps the reference's
     # float32 arithmetic per tile (sgp.py:648-666; include/bsgp.h gn_f32)
     f32 = (image.dtype == torch.float32) if torch.is_tensor(image) else \
@@ -162,7 +178,8 @@ def sgp_subdivisions(image, psf, bkg, subdiv_shape=(256, 256), overlap=32, betaP
 
 
 def sgp_subdivisions_multistart(image, psf, bkg, betas=None, score=None, subdiv_shape=(256, 256),
-                                overlap=32, **sgp_kwargs):
+                                overlap=32, bkg_box_size=None, bkg_filter_size=(3, 3),
+                                **sgp_kwargs):
     """The application's beta search for every subdivision of a field at once
     (application_sgp_subdivisions.py:69-107 per tile): the (tile x candidate)
     product -- n tiles x K initial betas (default: the application's five
@@ -176,13 +193,15 @@ def sgp_subdivisions_multistart(image, psf, bkg, betas=None, score=None, subdiv_
     ``score(x, tile)`` (host arrays of one candidate and its observed tile)
     stands in for the application's photometric score (photutils, absent
     here); without one the final discrepancy ranks the candidates.  ``psf``,
-    ``bkg`` and the keyword arguments as in :func:`sgp_subdivisions`.
+    ``bkg`` (``"estimate"`` with ``bkg_box_size`` included) and the keyword
+    arguments as in :func:`sgp_subdivisions`.
     Returns (mosaic, footprint, info): info holds the boxes, "betas",
     "scores" [n, K], "best" [n] (candidate index per tile), "best_beta" [n],
     and the solve outputs of the chosen candidates ("x", "iters", "discr",
     "beta_final")."""
     import sgp
     torch = _B.torch
+    bkg = _estimate_bkg(image, bkg, bkg_box_size, bkg_filter_size)
     betas = list(sgp.app_beta_candidates() if betas is None else betas)
     K = len(betas)
     f32 = (image.dtype == torch.float32) if torch.is_tensor(image) else \

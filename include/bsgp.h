@@ -253,6 +253,37 @@ int bsgp_coadd_tiles(const double* tiles, int32_t n, int32_t th, int32_t tw, con
 int bsgp_fits_to_f64(const void* raw, int64_t n, int32_t bitpix, double bscale, double bzero,
                      double* out, void* stream);
 
+/* Sky background of B images [B][H][W] on the device: the estimator
+ * restoration/utils.py:235-239 builds with photutils, Background2D(data,
+ * box_size, filter_size, bkg_estimator=MedianBackground()) with its default
+ * SigmaClip(sigma, maxiters), exclude_percentile and pad-and-mask edges,
+ * restated from astropy.stats.SigmaClip and scipy.ndimage:
+ * per bh x bw box the sigma-clipped median and population std of its valid
+ * pixels (inside the image, finite, mask byte 0); boxes with more than
+ * exclude_percentile/100 * bh*bw invalid pixels are filled from the 10 nearest
+ * kept cells (inverse distance); both meshes are median-filtered over fh x fw
+ * cells (odd, <= 7) and zoomed by cubic B-spline to [H][W], clamped to the
+ * filtered mesh's range if clip.
+ *   data        device, float32 or float64 (dtype = BSGP_DTYPE_*), widened to
+ *               float64 before any arithmetic
+ *   mask        device bytes [B][H][W], nonzero = masked, or NULL
+ *   bkg_out, rms_out            [B][H][W] maps
+ *   mesh_out, rms_mesh_out      [B][ny][nx] filtered meshes, ny = ceil(H/bh)
+ *   medians_out                 [B][2] medians of the two filtered meshes
+ *   status_out  int32 [B][1 + 3*ny*nx]: the number of kept boxes (0: every box
+ *               was excluded and the image's outputs are NaN), then per cell
+ *               the excluded flag, the pixels that survived clipping and the
+ *               clipping iterations run
+ * Every output pointer may be NULL.  bh*bw <= 4096 and ny*nx <= 4096, else
+ * BSGP_ERR_UNSUPPORTED.  Asynchronous (stream-ordered workspace). */
+#define BSGP_DTYPE_F32 0
+#define BSGP_DTYPE_F64 1
+int bsgp_background2d(const void* data, int32_t dtype, int32_t B, int32_t H, int32_t W, int32_t bh,
+                      int32_t bw, int32_t fh, int32_t fw, double sigma, int32_t maxiters,
+                      double exclude_percentile, int32_t clip, const uint8_t* mask, double* bkg_out,
+                      double* rms_out, double* mesh_out, double* rms_mesh_out, double* medians_out,
+                      int32_t* status_out, void* stream);
+
 /* DIAPL PSF model: the values of a psf*.bin.txt coefficient file
  * (psf/psf_calculate.py:10-47 reads them in this order) plus the degrees the
  * reference evaluates with (ldeg = 2, sdeg = 1: psf_calculate.py:24-25). */
