@@ -161,6 +161,10 @@ def lib():
             L.bsgp_solve_resume.argtypes = [vp, i32, vp, vp, i32, i64, vp, vp, vp]
             L.bsgp_background2d.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, i32, dbl, i32,
                                             dbl, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+            L.bsgp_convolve2d.argtypes = [vp, i32, i32, i32, i32, vp, i32, i32, vp, vp]
+            L.bsgp_detect_sources.argtypes = [vp, i32, i32, i32, i32, vp, dbl, i32, i32, vp, vp,
+                                              vp, vp]
+            L.bsgp_segment_catalog.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]
             for name in ["bsgp_plan_create", "bsgp_plan_create_checked", "bsgp_plan_destroy", "bsgp_plan_info",
                          "bsgp_solve_device", "bsgp_solve_host", "bsgp_solve_profiled",
                          "bsgp_apply_operator",
@@ -169,7 +173,8 @@ def lib():
                          "bsgp_extract_tiles", "bsgp_coadd_tiles", "bsgp_fits_to_f64",
                          "bsgp_psf_stamps", "bsgp_plan_set_psfs", "bsgp_state_layout",
                          "bsgp_state_bytes", "bsgp_state_save", "bsgp_solve_resume",
-                         "bsgp_background2d"]:
+                         "bsgp_background2d", "bsgp_convolve2d", "bsgp_detect_sources",
+                         "bsgp_segment_catalog"]:
                 getattr(L, name).restype = ctypes.c_int
             if L.bsgp_abi_version() != ABI_VERSION:
                 raise BsgpError(-3, f"{LIB_PATH} has ABI {L.bsgp_abi_version()}, this binding "
@@ -183,7 +188,8 @@ EXPORTED = ["bsgp_plan_create", "bsgp_plan_create_checked", "bsgp_plan_destroy",
             "bsgp_beta_div_deriv", "bsgp_beta_div_grad_parts", "bsgp_device_synchronize",
             "bsgp_last_error", "bsgp_abi_version", "bsgp_extract_tiles", "bsgp_coadd_tiles",
             "bsgp_fits_to_f64", "bsgp_psf_stamps", "bsgp_plan_set_psfs", "bsgp_state_layout",
-            "bsgp_state_bytes", "bsgp_state_save", "bsgp_solve_resume", "bsgp_background2d"]
+            "bsgp_state_bytes", "bsgp_state_save", "bsgp_solve_resume", "bsgp_background2d",
+            "bsgp_convolve2d", "bsgp_detect_sources", "bsgp_segment_catalog"]
 
 
 def check(rc):

@@ -1546,6 +1546,91 @@ int bsgp_background2d(const void* data, int32_t dtype, int32_t B, int32_t H, int
   return BSGP_OK;
 }
 
+namespace {
+// shape checks shared by the segmentation entry points
+int seg_shape(int32_t B, int32_t H, int32_t W) {
+  if (B < 1 || H < 1 || W < 1) return fail(BSGP_ERR_ARG, "B, H and W must be >= 1");
+  if ((int64_t)H * W > 0x7fffffffLL)
+    return fail(BSGP_ERR_UNSUPPORTED, "an image holds fewer than 2^31 pixels (H * W < 2^31)");
+  if (B > 65535) return fail(BSGP_ERR_UNSUPPORTED, "B must be at most 65535");
+  return BSGP_OK;
+}
+}  // namespace
+
+int bsgp_convolve2d(const void* data, int32_t dtype, int32_t B, int32_t H, int32_t W,
+                    const double* kernel, int32_t kh, int32_t kw, double* out, void* stream) {
+  if (!data) return fail(BSGP_ERR_ARG, "data is NULL");
+  if (!kernel) return fail(BSGP_ERR_ARG, "kernel is NULL");
+  if (!out) return fail(BSGP_ERR_ARG, "out is NULL");
+  if (dtype != BSGP_DTYPE_F32 && dtype != BSGP_DTYPE_F64)
+    return fail(BSGP_ERR_ARG, "dtype must be BSGP_DTYPE_F32 or BSGP_DTYPE_F64");
+  if (kh < 1 || kw < 1) return fail(BSGP_ERR_ARG, "kernel size (kh, kw) must be >= 1");
+  if (int rc = seg_shape(B, H, W)) return rc;
+  if (kh % 2 == 0 || kw % 2 == 0 || kh > kSegMaxKernel || kw > kSegMaxKernel) {
+    char msg[128];
+    snprintf(msg, sizeof msg, "kernel of %d x %d: kernels are odd and at most %d x %d", kh, kw,
+             kSegMaxKernel, kSegMaxKernel);
+    return fail(BSGP_ERR_UNSUPPORTED, msg);
+  }
+  if (H > 65535) return fail(BSGP_ERR_UNSUPPORTED, "H must be at most 65535");
+  SegConvArgs a{};
+  a.data = data, a.kernel = kernel, a.out = out;
+  a.B = B, a.H = H, a.W = W, a.kh = kh, a.kw = kw;
+  HIP_TRY(launch_seg_convolve(a, dtype == BSGP_DTYPE_F32, (hipStream_t)stream));
+  return BSGP_OK;
+}
+
+int bsgp_detect_sources(const void* data, int32_t dtype, int32_t B, int32_t H, int32_t W,
+                        const double* threshold_map, double threshold, int32_t npixels,
+                        int32_t connectivity, const uint8_t* mask, int32_t* labels_out,
+                        int32_t* nlabels_out, void* stream) {
+  if (!data) return fail(BSGP_ERR_ARG, "data is NULL");
+  if (!labels_out || !nlabels_out) return fail(BSGP_ERR_ARG, "labels_out / nlabels_out is NULL");
+  if (dtype != BSGP_DTYPE_F32 && dtype != BSGP_DTYPE_F64)
+    return fail(BSGP_ERR_ARG, "dtype must be BSGP_DTYPE_F32 or BSGP_DTYPE_F64");
+  if (npixels < 1) return fail(BSGP_ERR_ARG, "npixels must be >= 1");
+  if (connectivity != 4 && connectivity != 8)
+    return fail(BSGP_ERR_ARG, "connectivity must be 4 or 8");
+  if (int rc = seg_shape(B, H, W)) return rc;
+  const size_t hw = (size_t)H * W;
+  SegArgs a{};
+  a.data = data, a.thr_map = threshold_map, a.mask = mask, a.thr = threshold;
+  a.B = B, a.H = H, a.W = W, a.npixels = npixels, a.conn = connectivity;
+  a.nblk = (int)((hw + kSegChunk - 1) / kSegChunk);
+  a.labels_out = labels_out, a.nlabels_out = nlabels_out;
+  hipStream_t s = (hipStream_t)stream;
+  // stream-ordered workspace: the call stays asynchronous
+  const size_t per = 2 * hw + (size_t)a.nblk;
+  void* w = nullptr;
+  HIP_TRY(hipMallocAsync(&w, (size_t)B * per * sizeof(int), s));
+  a.lab = static_cast<int*>(w);
+  a.area = a.lab + (size_t)B * hw;
+  a.blk = a.area + (size_t)B * hw;
+  const hipError_t e = launch_seg_detect(a, dtype == BSGP_DTYPE_F32, s);
+  const hipError_t ef = hipFreeAsync(w, s);
+  if (e != hipSuccess) return fail(BSGP_ERR_HIP, std::string("detection launch: ") + hipGetErrorString(e));
+  HIP_TRY(ef);
+  return BSGP_OK;
+}
+
+int bsgp_segment_catalog(const double* data, const double* conv, const int32_t* labels, int32_t B,
+                         int32_t H, int32_t W, int32_t cap, const int32_t* nlabels,
+                         int32_t* int_cols_out, double* f64_cols_out, int32_t* status_out,
+                         void* stream) {
+  if (!data) return fail(BSGP_ERR_ARG, "data is NULL");
+  if (!labels) return fail(BSGP_ERR_ARG, "labels is NULL");
+  if (!int_cols_out || !f64_cols_out || !status_out)
+    return fail(BSGP_ERR_ARG, "int_cols_out / f64_cols_out / status_out is NULL");
+  if (cap < 1) return fail(BSGP_ERR_ARG, "cap must be >= 1");
+  if (int rc = seg_shape(B, H, W)) return rc;
+  SegCatArgs a{};
+  a.data = data, a.conv = conv, a.labels = labels, a.nlabels = nlabels;
+  a.B = B, a.H = H, a.W = W, a.cap = cap;
+  a.icols = int_cols_out, a.fcols = f64_cols_out, a.status = status_out;
+  HIP_TRY(launch_seg_catalog(a, (hipStream_t)stream));
+  return BSGP_OK;
+}
+
 int bsgp_beta_div(int64_t n, const double* y, const double* x, double beta, double* out,
                   void* stream) {
   if (n < 1 || n > 0x7fffffff || !y || !x || !out) return fail(BSGP_ERR_ARG, "bad arguments");

@@ -148,6 +148,40 @@ struct BkgArgs {
 hipError_t launch_bkg_boxstats(const BkgArgs& a, int f32, hipStream_t s);
 hipError_t launch_bkg_mesh(const BkgArgs& a, hipStream_t s);
 hipError_t launch_bkg_zoom(const BkgArgs& a, hipStream_t s);
+// ---- source detection (bsgp_segment.hip) ----------------------
+constexpr int kSegMaxKernel = 7;  // convolution kernel, per axis (odd)
+constexpr int kSegChunk = 2048;   // pixels one workgroup numbers in the compaction
+struct SegConvArgs {
+  const void* data;      // [B][H][W] float32 or float64
+  const double* kernel;  // [kh][kw] on the device
+  double* out;           // [B][H][W]
+  int B, H, W, kh, kw;
+};
+struct SegArgs {
+  const void* data;           // [B][H][W] float32 or float64
+  const double* thr_map;      // [B][H][W], or nullptr: thr
+  const unsigned char* mask;  // [B][H][W] bytes, nonzero = never detected, or nullptr
+  double thr;
+  int B, H, W, npixels, conn, nblk;  // nblk: chunks of kSegChunk pixels per image
+  int* lab;                          // workspace [B][H*W]: union-find parents (-1: background)
+  int* area;                         // workspace [B][H*W]: a root's area, then its final label
+  int* blk;                          // workspace [B][nblk]: kept roots per chunk, then their scan
+  int* labels_out;                   // [B][H][W]
+  int* nlabels_out;                  // [B]
+};
+struct SegCatArgs {
+  const double* data;  // [B][H][W]
+  const double* conv;  // [B][H][W], or nullptr: data
+  const int* labels;   // [B][H][W]
+  const int* nlabels;  // [B], or nullptr: cap
+  int B, H, W, cap;
+  int* icols;     // [B][cap][5]: area, xmin, xmax, ymin, ymax
+  double* fcols;  // [B][cap][8]: flux, min, max, xc, yc, sigx2, sigxy, sigy2
+  int* status;    // [B]: bit 0 nlabels > cap, bit 1 a label outside 1..min(cap, nlabels)
+};
+hipError_t launch_seg_convolve(const SegConvArgs& a, int f32, hipStream_t s);
+hipError_t launch_seg_detect(const SegArgs& a, int f32, hipStream_t s);
+hipError_t launch_seg_catalog(const SegCatArgs& a, hipStream_t s);
 struct PsfModel;
 hipError_t launch_psf_stamps(const PsfModel& m, const double* xy, int n, int spatial,
                              int normalize, double* out, hipStream_t s);

@@ -1,0 +1,432 @@
+"""Source detection and segment fluxes on the device.
+
+The reference's ``utils.source_info`` (restoration/utils.py:219-247) runs
+photutils: ``Background2D``, ``convolve`` with ``make_2dgaussian_kernel(1.2, 3)``,
+``SourceFinder(npixels, ...)`` and ``SourceCatalog``.  The application uses its
+result for the flux constraint of every solve,
+``flux=orig_scat['segment_flux'].value.sum()``
+(application_sgp_subdivisions.py:88,104,113), and for the score that ranks the
+beta candidates, ``1 - sum(segment_flux(restored)) / sum(segment_flux(original))``
+(:92-99).  This module computes both with ``bsgp_convolve2d``,
+``bsgp_detect_sources`` and ``bsgp_segment_catalog`` (include/bsgp.h; semantics
+in DESIGN §3.8) and keeps photutils' names.
+
+What is pinned and what is not: the kernel equals astropy's at rtol 1e-13, the
+convolution equals astropy's to the last bit, the label image equals ``scipy.ndimage.label`` followed by the
+removal of small components and a consecutive relabel, which is photutils'
+``detect_sources``.  Deblending (``SourceFinder(deblend=True)``) is not done: it
+splits a segment among children without dropping a pixel, so the sum of
+``segment_flux`` over all segments -- the only quantity the application uses --
+is the same with and without it, while the per-segment columns here describe
+undeblended segments.  The moment and shape columns are defined in DESIGN
+§3.8, modelled on photutils' documentation but not pinned to it.
+"""
+import warnings
+
+import numpy as np
+
+import _bsgp as _B
+
+FWHM_TO_SIGMA = 1.0 / (2.0 * np.sqrt(2.0 * np.log(2.0)))
+MAX_KERNEL = 7
+
+INT_COLUMNS = ("area", "bbox_xmin", "bbox_xmax", "bbox_ymin", "bbox_ymax")
+F64_COLUMNS = ("segment_flux", "min_value", "max_value", "xcentroid", "ycentroid",
+               "covar_sigx2", "covar_sigxy", "covar_sigy2")
+SHAPE_COLUMNS = ("semimajor_sigma", "semiminor_sigma", "orientation", "eccentricity",
+                 "ellipticity", "fwhm")
+COLUMNS = ("label",) + INT_COLUMNS + F64_COLUMNS + SHAPE_COLUMNS
+UNAVAILABLE = {
+    "sky_centroid": "there is no WCS here: use xcentroid / ycentroid",
+    "local_background": "data is background-subtracted; no local annulus is measured",
+    "segment_fluxerr": "no error array is carried: photometric errors are out of scope",
+}
+
+
+class NoDetectionsWarning(UserWarning):
+    """No source was found (photutils' warning of the same name)."""
+
+
+def make_2dgaussian_kernel(fwhm, size, mode="oversample", oversample=10):
+    """photutils' ``make_2dgaussian_kernel``: astropy's
+    ``Gaussian2DKernel(fwhm * gaussian_fwhm_to_sigma, x_size=size, y_size=size,
+    mode='oversample', factor=oversample)``, normalised to sum 1 (host, numpy).
+    Every pixel is the mean of the Gaussian over oversample x oversample
+    sub-pixel centres; ``mode='center'`` samples the pixel centres."""
+    if int(size) != size or size < 1 or int(size) % 2 == 0:
+        raise ValueError(f"size must be an odd positive int, got {size!r}")
+    if not fwhm > 0:
+        raise ValueError(f"fwhm must be positive, got {fwhm!r}")
+    if mode not in ("oversample", "center"):
+        raise ValueError(f"mode must be 'oversample' or 'center', got {mode!r}")
+    size = int(size)
+    f = int(oversample) if mode == "oversample" else 1
+    if f < 1:
+        raise ValueError(f"oversample must be >= 1, got {oversample!r}")
+    sigma = fwhm * FWHM_TO_SIGMA
+    lo, hi = -(size // 2), size // 2 + 1
+    x = np.linspace(lo - 0.5 * (1 - 1 / f), hi - 0.5 * (1 + 1 / f), num=int((hi - lo) * f))
+    xg, yg = np.meshgrid(x, x)
+    # astropy's Gaussian2D.evaluate at theta = 0, operation for operation
+    a = 0.5 * (1.0 / sigma ** 2 + 0.0 / sigma ** 2)
+    v = 1.0 / (2 * np.pi * sigma * sigma) * np.exp(-((a * xg ** 2) + (0.0 * xg * yg) + (a * yg ** 2)))
+    v = v.reshape(size, f, size, f).mean(axis=3).mean(axis=1)
+    return v / v.sum()
+
+
+def _check_kernel(kernel):
+    k = np.asarray(kernel, dtype=np.float64)
+    if k.ndim != 2:
+        raise ValueError(f"kernel must be 2-D, got shape {k.shape}")
+    kh, kw = k.shape
+    if kh % 2 == 0 or kw % 2 == 0 or kh > MAX_KERNEL or kw > MAX_KERNEL:
+        raise ValueError(f"kernel of {kh} x {kw}: kernels are odd and at most "
+                         f"{MAX_KERNEL} x {MAX_KERNEL}")
+    if not np.all(np.isfinite(k)) or k.sum() == 0:
+        raise ValueError("kernel must be finite with a nonzero sum")
+    return np.ascontiguousarray(k)
+
+
+def _shape_of(a):
+    torch = _B.torch
+    return tuple(a.shape) if torch is not None and torch.is_tensor(a) else np.shape(a)
+
+
+def _check_image_shape(shape, name="data"):
+    if len(shape) not in (2, 3) or 0 in shape:
+        raise ValueError(f"{name} must be [H, W] or [B, H, W], got shape {tuple(shape)}")
+
+
+def _to_dev(data, keep_f32=True):
+    """float32 / float64 CUDA tensor [B, H, W] and whether data was a batch."""
+    torch = _B.torch
+    if torch.is_tensor(data):
+        ok = (torch.float32, torch.float64) if keep_f32 else (torch.float64,)
+        d = data if data.dtype in ok else data.to(torch.float64)
+        d = d.to("cuda").contiguous()
+    else:
+        d = np.asarray(data)
+        if not (d.dtype.kind == "f" and d.dtype.itemsize in ((4, 8) if keep_f32 else (8,))):
+            d = d.astype(np.float64)
+        d = torch.from_numpy(np.ascontiguousarray(d.astype(d.dtype.newbyteorder("=")))).to("cuda")
+    batched = d.dim() == 3
+    return (d if batched else d[None]), batched
+
+
+def _dtype(d):
+    return _B.BSGP_DTYPE_F32 if d.dtype == _B.torch.float32 else _B.BSGP_DTYPE_F64
+
+
+def _out(t, batched, device_out):
+    t = t if batched else t[0]
+    return t if device_out else t.cpu().numpy()
+
+
+def convolve(data, kernel, device_out=False):
+    """``astropy.convolution.convolve(data, kernel)`` with its defaults on
+    finite input: zero fill, kernel normalised by its sum.  float64 result of
+    data's shape.  A non-finite pixel raises ``ValueError`` (astropy's NaN
+    interpolation is not offered)."""
+    _check_image_shape(_shape_of(data))
+    k = _check_kernel(kernel)
+    _B.require_gpu()
+    torch = _B.torch
+    d, batched = _to_dev(data)
+    if not bool(torch.isfinite(d).all()):
+        raise ValueError("data holds non-finite pixels: NaN interpolation is not offered")
+    return _out(_convolve_dev(d, k), batched, device_out)
+
+
+def _convolve_dev(d, k):
+    torch = _B.torch
+    B, H, W = d.shape
+    kd = torch.from_numpy(k).to("cuda")
+    out = torch.empty((B, H, W), dtype=torch.float64, device="cuda")
+    _B.check(_B.lib().bsgp_convolve2d(_B._ptr(d), _dtype(d), B, H, W, _B._ptr(kd), k.shape[0],
+                                      k.shape[1], _B._ptr(out), _B.current_stream()))
+    out._keep = (d, kd)
+    return out
+
+
+class SegmentationImage:
+    """Result of :func:`detect_sources`: ``data`` (int32 label image, 0 =
+    background), ``nlabels``, ``labels`` (1..nlabels) and ``areas`` (pixels per
+    label).  For a batch ``data`` is [B, H, W], ``nlabels`` an int array [B]
+    and ``labels`` / ``areas`` lists of B arrays."""
+
+    def __init__(self, data, nlabels, batched):
+        self.data, self.batched = data, batched
+        self.nlabels = nlabels if batched else int(nlabels[0])
+        self._n = np.asarray(nlabels)
+
+    @property
+    def labels(self):
+        out = [np.arange(1, n + 1, dtype=np.int32) for n in self._n]
+        return out if self.batched else out[0]
+
+    @property
+    def areas(self):
+        torch = _B.torch
+        lab = self.data if self.batched else self.data[None]
+        lab = lab.cpu().numpy() if torch is not None and torch.is_tensor(lab) else np.asarray(lab)
+        out = [np.bincount(l.ravel(), minlength=n + 1)[1:] for l, n in zip(lab, self._n)]
+        return out if self.batched else out[0]
+
+
+def check_detect_args(shape, npixels, connectivity, threshold_shape=(), mask_shape=None):
+    """The argument checks of detect_sources (host only)."""
+    _check_image_shape(shape)
+    if int(npixels) != npixels or npixels < 1:
+        raise ValueError(f"npixels must be a positive int, got {npixels!r}")
+    if connectivity not in (4, 8):
+        raise ValueError(f"connectivity must be 4 or 8, got {connectivity!r}")
+    for nm, s in (("threshold", threshold_shape), ("mask", mask_shape)):
+        if s is None or (nm == "threshold" and tuple(s) == ()):
+            continue
+        if tuple(s) != tuple(shape) and tuple(s) != tuple(shape[-2:]):
+            raise ValueError(f"{nm} shape {tuple(s)} does not match data shape {tuple(shape)}")
+
+
+def detect_sources(data, threshold, npixels, connectivity=8, mask=None, device_out=False):
+    """photutils' ``detect_sources``: pixels with ``data > threshold`` (a
+    scalar or a map; masked or non-finite pixels never), grouped with 8- or
+    4-connectivity, groups of fewer than ``npixels`` pixels removed, the others
+    numbered 1..n by their first pixel in raster order.  An unbatched call that
+    detects nothing warns and returns ``None``; in a batch such an image has
+    ``nlabels == 0``."""
+    check_detect_args(_shape_of(data), npixels, connectivity, _shape_of(threshold),
+                      None if mask is None else _shape_of(mask))
+    _B.require_gpu()
+    d, batched = _to_dev(data)
+    seg = _detect_dev(d, threshold, int(npixels), int(connectivity), mask)
+    lab, n = seg
+    if not batched and n[0] == 0:
+        warnings.warn("No sources were found.", NoDetectionsWarning)
+        return None
+    return SegmentationImage(_out(lab, batched, device_out), n, batched)
+
+
+def _detect_dev(d, threshold, npixels, connectivity, mask):
+    """(int32 CUDA labels [B, H, W], host nlabels [B]); one synchronisation."""
+    torch = _B.torch
+    B, H, W = d.shape
+    thr_map, thr = None, 0.0
+    if torch.is_tensor(threshold) or np.ndim(threshold) > 0:
+        t, _ = _to_dev(threshold, keep_f32=False)
+        thr_map = t.expand(B, H, W).contiguous()
+    else:
+        thr = float(threshold)
+    m = None
+    if mask is not None:
+        m = mask if torch.is_tensor(mask) else torch.from_numpy(np.ascontiguousarray(np.asarray(mask) != 0))
+        m = (m != 0).to("cuda")
+        m = (m[None] if m.dim() == 2 else m).expand(B, H, W).to(torch.uint8).contiguous()
+    lab = torch.empty((B, H, W), dtype=torch.int32, device="cuda")
+    n = torch.empty((B,), dtype=torch.int32, device="cuda")
+    _B.check(_B.lib().bsgp_detect_sources(_B._ptr(d), _dtype(d), B, H, W, _B._ptr(thr_map), thr,
+                                          npixels, connectivity, _B._ptr(m), _B._ptr(lab),
+                                          _B._ptr(n), _B.current_stream()))
+    return lab, n.cpu().numpy()  # waits for the kernels (d, thr_map, m are alive until here)
+
+
+def shape_columns(sigx2, sigxy, sigy2):
+    """The shape columns from the covariance of a segment's convolved pixels,
+    by the formulas of photutils' documentation: a^2 and b^2 are the
+    eigenvalues of [[sigx2, sigxy], [sigxy, sigy2]] (negative rounding residue
+    clipped to 0), orientation = atan2(2 sigxy, sigx2 - sigy2) / 2 in degrees
+    (counterclockwise from +x), eccentricity = sqrt(1 - b^2 / a^2),
+    ellipticity = 1 - b / a, fwhm = 2 sqrt(ln 2 (a^2 + b^2))."""
+    sx, sxy, sy = (np.asarray(v, dtype=np.float64) for v in (sigx2, sigxy, sigy2))
+    half, root = (sx + sy) / 2, np.sqrt(((sx - sy) / 2) ** 2 + sxy ** 2)
+    a2, b2 = np.maximum(half + root, 0.0), np.maximum(half - root, 0.0)
+    a, b = np.sqrt(a2), np.sqrt(b2)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        ecc, ell = np.sqrt(1.0 - b2 / a2), 1.0 - b / a
+    return dict(semimajor_sigma=a, semiminor_sigma=b,
+                orientation=np.degrees(0.5 * np.arctan2(2.0 * sxy, sx - sy)),
+                eccentricity=ecc, ellipticity=ell, fwhm=2.0 * np.sqrt(np.log(2.0) * (a2 + b2)))
+
+
+class SourceCatalog:
+    """``SourceCatalog(data, segment_img, convolved_data=None)`` on the device.
+
+    ``data`` is already background-subtracted, as ``source_info`` passes it
+    (``background`` is accepted for photutils' signature and only kept).
+    ``segment_img``: a :class:`SegmentationImage` or an integer label image.
+    Attributes, one entry per label (a batch: a list of B arrays each):
+    ``label``, ``area``, ``bbox_xmin`` / ``bbox_xmax`` / ``bbox_ymin`` /
+    ``bbox_ymax`` (inclusive), ``segment_flux``, ``min_value``, ``max_value`` (of
+    ``data``), ``xcentroid``, ``ycentroid``, ``covar_sigx2`` / ``covar_sigxy`` /
+    ``covar_sigy2`` (first and central second moments of ``convolved_data``, or
+    of ``data`` without one) and from those ``semimajor_sigma``,
+    ``semiminor_sigma``, ``orientation`` (degrees), ``eccentricity``,
+    ``ellipticity``, ``fwhm`` (:func:`shape_columns`).  ``segment_flux_sum`` is
+    the sum over all segments -- the deblend-invariant quantity the
+    application uses -- per image.  The columns describe undeblended segments;
+    the moment and shape columns are modelled on photutils, not pinned to it.
+    ``sky_centroid``, ``local_background`` and ``segment_fluxerr`` raise
+    ``KeyError`` with the reason.  ``device_out=True`` adds ``int_cols`` /
+    ``f64_cols`` (CUDA tensors [B, cap, 5] / [B, cap, 8])."""
+
+    def __init__(self, data, segment_img, convolved_data=None, background=None, device_out=False):
+        torch = _B.torch
+        shape = _shape_of(data)
+        _check_image_shape(shape)
+        seg = segment_img.data if isinstance(segment_img, SegmentationImage) else segment_img
+        if _shape_of(seg) != shape:
+            raise ValueError(f"segment_img shape {_shape_of(seg)} does not match data shape {shape}")
+        if convolved_data is not None and _shape_of(convolved_data) != shape:
+            raise ValueError(f"convolved_data shape {_shape_of(convolved_data)} does not match "
+                             f"data shape {shape}")
+        _B.require_gpu()
+        d, batched = _to_dev(data, keep_f32=False)
+        c = None if convolved_data is None else _to_dev(convolved_data, keep_f32=False)[0]
+        lab = seg if torch.is_tensor(seg) else torch.from_numpy(np.ascontiguousarray(seg))
+        lab = lab.to(device="cuda", dtype=torch.int32).contiguous()
+        lab = lab if batched else lab[None]
+        if isinstance(segment_img, SegmentationImage):
+            n = np.asarray(segment_img._n, dtype=np.int32)
+        else:
+            if bool((lab < 0).any()):
+                raise ValueError("segment_img holds negative labels")
+            n = lab.reshape(lab.shape[0], -1).amax(dim=1).cpu().numpy().astype(np.int32)
+        self._fill(d, c, lab, n, batched, device_out)
+        self.background = background
+
+    def _fill(self, d, c, lab, n, batched, device_out):
+        torch = _B.torch
+        B, H, W = d.shape
+        cap = max(1, int(n.max()))
+        nd = torch.from_numpy(np.ascontiguousarray(n)).to("cuda")
+        ic = torch.empty((B, cap, 5), dtype=torch.int32, device="cuda")
+        fc = torch.empty((B, cap, 8), dtype=torch.float64, device="cuda")
+        st = torch.empty((B,), dtype=torch.int32, device="cuda")
+        _B.check(_B.lib().bsgp_segment_catalog(_B._ptr(d), _B._ptr(c), _B._ptr(lab), B, H, W, cap,
+                                               _B._ptr(nd), _B._ptr(ic), _B._ptr(fc), _B._ptr(st),
+                                               _B.current_stream()))
+        ich, fch, sth = ic.cpu().numpy(), fc.cpu().numpy(), st.cpu().numpy()
+        if sth.any():
+            raise _B.BsgpError(_B.BSGP_ERR_ARG, f"image {int(np.flatnonzero(sth)[0])}: labels "
+                               "outside 1..nlabels in the segmentation image")
+        self.batched, self.nlabels = batched, (n if batched else int(n[0]))
+        if device_out:
+            self.int_cols, self.f64_cols = ic, fc
+        cols = {"label": [np.arange(1, k + 1, dtype=np.int32) for k in n]}
+        for j, nm in enumerate(INT_COLUMNS):
+            cols[nm] = [ich[b, :n[b], j] for b in range(B)]
+        for j, nm in enumerate(F64_COLUMNS):
+            cols[nm] = [fch[b, :n[b], j] for b in range(B)]
+        shp = [shape_columns(fch[b, :n[b], 5], fch[b, :n[b], 6], fch[b, :n[b], 7]) for b in range(B)]
+        for nm in SHAPE_COLUMNS:
+            cols[nm] = [s[nm] for s in shp]
+        self._cols = cols
+        # one fixed order for the total as well: numpy's sum of the per-segment fluxes
+        tot = np.array([float(np.sum(v)) for v in cols["segment_flux"]])
+        self.segment_flux_sum = tot if batched else float(tot[0])
+
+    def __getattr__(self, name):
+        if name.startswith("_"):
+            raise AttributeError(name)
+        try:
+            return self[name]
+        except KeyError as e:
+            raise AttributeError(str(e)) from None
+
+    def __getitem__(self, name):
+        if name in UNAVAILABLE:
+            raise KeyError(f"{name} is not available: {UNAVAILABLE[name]}")
+        if name not in self._cols:
+            raise KeyError(f"unknown column {name!r}; available: {', '.join(COLUMNS)}")
+        v = self._cols[name]
+        return v if self.batched else v[0]
+
+    def __len__(self):
+        return int(np.sum(self.nlabels))
+
+    def to_dict(self, columns=None):
+        """The named columns (default: all) as a dict; unknown and unavailable
+        names raise ``KeyError``."""
+        return {k: self[k] for k in (COLUMNS if columns is None else columns)}
+
+
+def source_info(data, box_size, n_pixels=5, sigma_threshold=1.5, device_out=False):
+    """``utils.source_info`` (restoration/utils.py:235-247) without the
+    deblending, for an image or a batch: ``Background2D(data, box_size,
+    filter_size=(3, 3))``, ``sub = data - background``, ``threshold =
+    sigma_threshold * background_rms``, ``conv = convolve(sub,
+    make_2dgaussian_kernel(1.2, 3))``, ``detect_sources(conv, threshold,
+    n_pixels)`` and the catalogue of ``sub`` with ``convolved_data=conv``.
+    Returns ``(catalog, bkg)``; the catalogue also carries ``segment_img``,
+    ``data`` (sub) and ``convolved_data``.  An unbatched image without a
+    detection warns and gives ``(None, bkg)``.  With ``device_out=True`` the
+    maps stay on the device."""
+    from background import Background2D
+    torch = _B.torch
+    _check_image_shape(_shape_of(data))
+    check_detect_args(_shape_of(data), n_pixels, 8)
+    bkg = Background2D(data, box_size, filter_size=(3, 3), device_out=True)
+    d, batched = _to_dev(data)
+    bg = bkg.background if batched else bkg.background[None]
+    rms = bkg.background_rms if batched else bkg.background_rms[None]
+    sub = d.to(torch.float64) - bg
+    thr = float(sigma_threshold) * rms
+    if not bool(torch.isfinite(sub).all()):
+        raise ValueError("data holds non-finite pixels: NaN interpolation is not offered")
+    conv = _convolve_dev(sub, make_2dgaussian_kernel(1.2, 3))
+    lab, n = _detect_dev(conv, thr, int(n_pixels), 8, None)
+    if not device_out:
+        for nm in ("background", "background_rms", "background_mesh", "background_rms_mesh"):
+            setattr(bkg, nm, getattr(bkg, nm).cpu().numpy())
+    if not batched and n[0] == 0:
+        warnings.warn("No sources were found.", NoDetectionsWarning)
+        return None, bkg
+    cat = SourceCatalog.__new__(SourceCatalog)
+    cat._fill(sub, conv, lab, n.astype(np.int32), batched, device_out)
+    cat.background = None
+    cat.segment_img = SegmentationImage(_out(lab, batched, device_out), n, batched)
+    cat.data, cat.convolved_data = _out(sub, batched, device_out), _out(conv, batched, device_out)
+    return cat, bkg
+
+
+def segment_flux_sums(images, box_size, n_pixels=5, sigma_threshold=1.5):
+    """Sum of ``segment_flux`` per image of a batch [B, H, W] (one batched
+    ``source_info``); 0.0 for an image without a detection."""
+    cat, _ = source_info(images, box_size, n_pixels, sigma_threshold, device_out=True)
+    return np.asarray(cat.segment_flux_sum, dtype=np.float64)
+
+
+def flux_fraction_score(gn, box_size=60, n_pixels_orig=5, n_pixels_restored=1,
+                        sigma_threshold=1.5):
+    """The application's beta-candidate score
+    (application_sgp_subdivisions.py:92-99) as a callable for the ``score=``
+    parameters of ``sgp_betaDiv_multistart`` and
+    ``sgp_subdivisions_multistart``: ``score(x)`` and ``score(x, tile)`` return
+    ``1 - sum(segment_flux(source_info(x, box_size, n_pixels_restored))) /
+    sum(segment_flux(source_info(gn or tile, box_size, n_pixels_orig)))``;
+    ``score.batch(xs)`` / ``score.batch(xs, tiles)`` evaluate candidates
+    [n, H, W] in one batched ``source_info`` (``tiles``: one observed image, or
+    one per candidate)."""
+    cache = {}
+
+    def orig(img):
+        """Flux sums of the observed image(s) [n, H, W] or [H, W] -> [n] or [1]."""
+        a = img if len(_shape_of(img)) == 3 else img[None]
+        return segment_flux_sums(a, box_size, n_pixels_orig, sigma_threshold)
+
+    def orig_gn():
+        if "gn" not in cache:
+            if gn is None:
+                raise ValueError("flux_fraction_score(None) needs the observed tile: score(x, tile)")
+            cache["gn"] = orig(gn)
+        return cache["gn"]
+
+    def batch(xs, tiles=None):
+        den = orig_gn() if tiles is None else orig(tiles)
+        num = segment_flux_sums(xs, box_size, n_pixels_restored, sigma_threshold)
+        return 1.0 - num / den
+
+    def score(x, tile=None):
+        return float(batch(x[None], tile)[0])
+
+    score.batch = batch
+    return score

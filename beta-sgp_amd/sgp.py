@@ -847,9 +847,10 @@ def sgp_betaDiv_multistart(gn, psf, bkg, betas=None, score=None, final_solve=Tru
     lines and its two printed lines, sgp.py:892-893, are repeated for it).
 
     ``score`` is the application's criterion, the photometric flux fractional
-    difference 1 - sum(segment_flux(x)) / sum(segment_flux(gn)) (:92-99); it
-    needs photutils, which this package does not carry, so the caller passes
-    it.  Without one the candidates are ranked by their final discrepancy
+    difference 1 - sum(segment_flux(x)) / sum(segment_flux(gn)) (:92-99):
+    ``segmentation.flux_fraction_score(gn, box_size)`` computes it on the
+    device (a score object with a ``batch`` method gets all candidates in one
+    call).  Without one the candidates are ranked by their final discrepancy
     discr[-1] (a stand-in, not the application's choice).  ``kwargs`` are
     sgp_betaDiv's keyword arguments.  ``devices=[...]`` spreads the
     candidates over GPUs (one batched launch per GPU).
@@ -891,7 +892,10 @@ def sgp_betaDiv_multistart(gn, psf, bkg, betas=None, score=None, final_solve=Tru
     else:
         runs = [r for part in on_devices(devices, len(betas), work) for r in part]
     cands = [(x, it, d, t, None) for x, it, d, t, _ in runs]
-    scores = [float(score(c[0])) if score is not None else float(c[2][-1]) for c in cands]
+    if hasattr(score, "batch"):  # all candidates in one batched evaluation
+        scores = [float(v) for v in score.batch(np.stack([np.asarray(c[0]) for c in cands]))]
+    else:
+        scores = [float(score(c[0])) if score is not None else float(c[2][-1]) for c in cands]
     best = argmin_strict(scores)
     if best is None:
         raise ValueError(f"no candidate has a finite score below +inf: {scores} (the reference "

@@ -135,6 +135,22 @@ def _estimate_bkg(image, bkg, box_size, filter_size):
     return Background2D(image, box_size, filter_size=filter_size, device_out=True).background
 
 
+def _segment_flux(sgp_kwargs, tiles, box_size, repeat=1):
+    """``flux="segments"``: every tile's flux constraint becomes the sum of
+    ``segment_flux`` of ``source_info(tile, bkg_box_size, n_pixels=5)``
+    (application_sgp_subdivisions.py:88,104,113: each subdivision's own
+    detection with its own background), all tiles in one batch; any other
+    ``flux`` stays as it is."""
+    if not isinstance(sgp_kwargs.get("flux"), str):
+        return
+    if sgp_kwargs["flux"] != "segments":
+        raise ValueError(f'flux must be a number, an array or "segments", got {sgp_kwargs["flux"]!r}')
+    if box_size is None:
+        raise ValueError('flux="segments" needs bkg_box_size (source_info\'s box_size)')
+    from segmentation import segment_flux_sums
+    sgp_kwargs["flux"] = np.repeat(segment_flux_sums(tiles, box_size, n_pixels=5), repeat)
+
+
 def sgp_subdivisions(image, psf, bkg, subdiv_shape=(256, 256), overlap=32, betaParams=None,
                      device_out=False, bkg_box_size=None, bkg_filter_size=(3, 3), **sgp_kwargs):
     """Field -> overlapping subdivisions -> one batched beta-SGP solve -> mean
@@ -145,6 +161,9 @@ def sgp_subdivisions(image, psf, bkg, subdiv_shape=(256, 256), overlap=32, betaP
     (x, y) = ((x0 + x1 - 1) / 2, (y0 + y1 - 1) / 2)) so each tile is solved
     with its own PSF.  ``bkg="estimate"`` estimates the map from the field
     itself with background.Background2D(image, bkg_box_size, bkg_filter_size).
+    ``flux="segments"`` gives every tile the application's flux constraint, the
+    sum of ``segment_flux`` of ``segmentation.source_info(tile, bkg_box_size,
+    n_pixels=5)``.
     Returns (mosaic, footprint, solve outputs); numpy unless device_out."""
     import sgp
     torch = _B.torch
@@ -166,6 +185,7 @@ def sgp_subdivisions(image, psf, bkg, subdiv_shape=(256, 256), overlap=32, betaP
         bk = torch.full((len(boxes),), float(b), dtype=torch.float64, device="cuda")
     if hasattr(psf, "stamps"):  # spatially varying DIAPL model: a stamp per tile centre
         psf = psf.stamps(tile_centres(boxes), normalize=True, device_out=True)
+    _segment_flux(sgp_kwargs, tiles, bkg_box_size)
     out = sgp.sgp_betaDiv_batch(tiles, psf, bk, betaParams=betaParams, device_out=True,
                                 **sgp_kwargs)
     mosaic, foot = coadd_tiles(out["x"], boxes, (H, W))
@@ -191,8 +211,11 @@ def sgp_subdivisions_multistart(image, psf, bkg, betas=None, score=None, subdiv_
     not run again.
 
     ``score(x, tile)`` (host arrays of one candidate and its observed tile)
-    stands in for the application's photometric score (photutils, absent
-    here); without one the final discrepancy ranks the candidates.  ``psf``,
+    is the application's photometric score; ``segmentation.flux_fraction_score(
+    None, box_size)`` computes it on the device (a score object with a ``batch``
+    method gets every candidate in one call); without one the final
+    discrepancy ranks the candidates.  ``flux="segments"`` as in
+    :func:`sgp_subdivisions`.  ``psf``,
     ``bkg`` (``"estimate"`` with ``bkg_box_size`` included) and the keyword
     arguments as in :func:`sgp_subdivisions`.
     Returns (mosaic, footprint, info): info holds the boxes, "betas",
@@ -224,16 +247,20 @@ def sgp_subdivisions_multistart(image, psf, bkg, betas=None, score=None, subdiv_
         pt = psf if torch.is_tensor(psf) else _B.to_dev(np.asarray(psf, dtype=np.float64))
         psf = pt.repeat_interleave(K, dim=0)
     gns = tiles.repeat_interleave(K, dim=0)
+    _segment_flux(sgp_kwargs, tiles, bkg_box_size, repeat=K)
     out = sgp.sgp_betaDiv_batch(gns, psf, bk, betaParams=np.tile(np.asarray(betas, float), n),
                                 **sgp_kwargs)
     t_host = tiles.cpu().numpy()
     scores = np.empty((n, K))
-    for t in range(n):
-        for k in range(K):
-            i = t * K + k
-            it = int(out["iters"][i])
-            scores[t, k] = (float(score(out["x"][i], t_host[t])) if score is not None
-                            else float(out["discr"][i, it]))
+    if hasattr(score, "batch"):  # all candidates of all tiles in one batched evaluation
+        scores[:] = np.asarray(score.batch(out["x"], gns)).reshape(n, K)
+    else:
+        for t in range(n):
+            for k in range(K):
+                i = t * K + k
+                it = int(out["iters"][i])
+                scores[t, k] = (float(score(out["x"][i], t_host[t])) if score is not None
+                                else float(out["discr"][i, it]))
     best = []
     for t in range(n):
         j = sgp.argmin_strict(scores[t])

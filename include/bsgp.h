@@ -403,6 +403,47 @@ int bsgp_solve_resume(bsgp_plan plan, int32_t B, const bsgp_params* params,
                       const void* state_dev, int32_t n_state, int64_t bytes_per_image,
                       const int32_t* index, const bsgp_outputs* out, void* stream);
 
+/* Source detection and segment measurement: the part of
+ * utils.source_info (restoration/utils.py:240-247) that precedes deblending.
+ * All three are asynchronous; images of a batch are processed on their own and
+ * get the bits they get alone; H * W < 2^31 and B <= 65535, else
+ * BSGP_ERR_UNSUPPORTED.
+ *
+ * bsgp_convolve2d: astropy.convolution.convolve(data, kernel) with its
+ * defaults on finite input (utils.py:242: boundary='fill', fill_value=0,
+ * normalize_kernel=True).  out = (sum_i sum_j P[y+i][x+j] * K[kh-1-i][kw-1-j])
+ * / sum(K), P the zero-padded input, every product rounded, rows outer, one
+ * division by numpy's sum of the kernel.  kernel: device float64 [kh][kw],
+ * odd and at most 7 x 7 (else BSGP_ERR_UNSUPPORTED).  data: float32 or float64
+ * (dtype), widened first; out: float64 [B][H][W]; H <= 65535. */
+int bsgp_convolve2d(const void* data, int32_t dtype, int32_t B, int32_t H, int32_t W,
+                    const double* kernel, int32_t kh, int32_t kw, double* out, void* stream);
+/* photutils' detect_sources (utils.py:243): a pixel is detected where data >
+ * threshold (threshold_map [B][H][W] float64, or the scalar when it is NULL),
+ * both finite and mask (bytes, nonzero = masked, or NULL) clear.  Components of
+ * connectivity 8 or 4 with fewer than npixels pixels are removed; the others
+ * are numbered 1..n by their first pixel in raster order (scipy.ndimage.label
+ * and a consecutive relabel).  labels_out: int32 [B][H][W], 0 = background;
+ * nlabels_out: int32 [B] on the device. */
+int bsgp_detect_sources(const void* data, int32_t dtype, int32_t B, int32_t H, int32_t W,
+                        const double* threshold_map, double threshold, int32_t npixels,
+                        int32_t connectivity, const uint8_t* mask, int32_t* labels_out,
+                        int32_t* nlabels_out, void* stream);
+/* The columns of photutils' SourceCatalog (utils.py:245-247) that need the
+ * pixels, per label 1..min(cap, nlabels[b]) of image b (nlabels: device int32
+ * [B], or NULL for cap): int_cols_out [B][cap][5] = area, bbox xmin, xmax,
+ * ymin, ymax (inclusive); f64_cols_out [B][cap][8] = segment_flux, min_value,
+ * max_value (of data), xcentroid, ycentroid, covar_sigx2, covar_sigxy,
+ * covar_sigy2 (moments of conv, or of data when conv is NULL).  Rows beyond
+ * an image's labels, and of labels it does not hold, have area 0 and zero
+ * float columns.
+ * status_out [B]: bit 0 nlabels[b] > cap, bit 1 a label outside
+ * 1..min(cap, nlabels[b]) was met; such labels are skipped, never written. */
+int bsgp_segment_catalog(const double* data, const double* conv, const int32_t* labels, int32_t B,
+                         int32_t H, int32_t W, int32_t cap, const int32_t* nlabels,
+                         int32_t* int_cols_out, double* f64_cols_out, int32_t* status_out,
+                         void* stream);
+
 int bsgp_device_synchronize(void);
 const char* bsgp_last_error(void);
 int32_t bsgp_abi_version(void);
