@@ -699,7 +699,7 @@ def _same_psf(plan, psf):
 
 # plan-layout overrides read by bsgp_plan_create (A/B knobs): part of the key,
 # so a pooled plan never keeps the layout of an earlier setting
-_PLAN_KNOBS = ("BSGP_PERWAVE_MIN_WG", "BSGP_PERWAVE_TW", "BSGP_COOP_ELEMS")
+_PLAN_KNOBS = ("BSGP_PERWAVE_MIN_WG", "BSGP_PERWAVE_TW", "BSGP_COOP_ELEMS", "BSGP_LS_PREDICT")
 
 
 def _plan_key(H, W, psf, conv_mode, storage):

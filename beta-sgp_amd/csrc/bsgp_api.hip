@@ -30,7 +30,7 @@ int fail(int code, const std::string& msg) {
 }
 
 // A/B override knobs (BSGP_PERWAVE_MIN_WG, BSGP_PERWAVE_TW, BSGP_COOP_ELEMS,
-// BSGP_FOLD_SETUP, BSGP_SPIN_LIMIT; environment variables, the default is the
+// BSGP_FOLD_SETUP, BSGP_SPIN_LIMIT, BSGP_LS_PREDICT; environment variables, the default is the
 // literal at the call): a value that is not a whole decimal number in [lo, hi]
 // is ignored and the default used, so a typo cannot turn into a
 // zero (a spin limit of 0 fails every persistent solve with a timeout).
@@ -627,11 +627,14 @@ int bsgp_plan_create_checked(int32_t H, int32_t W, const double* psf, int32_t kh
   const size_t N = (size_t)H * W;
   p->storage = storage;
   // slot: gn and bkg in float64 (vec_stride each), the seven iteration vectors
-  // in the storage type, then the half spectrum (complex float64)
+  // in the storage type, then the half spectrum (complex float64), then two
+  // more vectors
   p->vec_stride = round_up(N, 32);
   const size_t vbytes = storage == BSGP_STORAGE_F32 ? sizeof(float) : sizeof(double);
   p->spec_off = 2 * p->vec_stride + 7 * p->vec_stride * vbytes / sizeof(double);
-  p->slot_stride = p->spec_off + round_up((size_t)g.sld * g.Qh * 2, 32);
+  // and, last, the second x_tf / pw pair (ImgState::par_tf; slot_bufs finds it
+  // from the slot's end)
+  p->slot_stride = p->spec_off + round_up((size_t)g.sld * g.Qh * 2, 32) + 2 * p->vec_stride;
   {
     const std::vector<int> prog = pairwise_program((long)N, &p->pw);
     if (hipMalloc(&p->pwprog, prog.size() * sizeof(int)) != hipSuccess ||
@@ -898,6 +901,7 @@ static int solve_impl(bsgp_plan p, int32_t B, const bsgp_params* prm, const bsgp
   a.storage = p->storage;
   a.spec_off = p->spec_off;
   a.spin_limit = (unsigned)env_knob("BSGP_SPIN_LIMIT", 1ll << 26, 0, 0xffffffffll);
+  a.ls_predict = (int)env_knob("BSGP_LS_PREDICT", 1, 0, 5);
   a.ls_cap = (prm->beta > 0.0 && prm->beta < 1.0)
                  ? (int)std::ceil(std::log(1e-12) / std::log(prm->beta)) + 2
                  : 4096;

@@ -48,7 +48,7 @@ constexpr int kSharedBytes = 512;  // LDS after the wave partials: reduced total
 // (tools/phase_prof.py reads them through bsgp_phase_prof).  Row passes given
 // a slot base PHS >= 0 split their time into operand batches (PHS), FFTs
 // (PHS + 1) and spectrum stores / staging (PHS + 2), as seen by wave 0.
-constexpr int kPhaseSlots = 32;
+constexpr int kPhaseSlots = 40;
 #ifdef BSGP_PHASE_PROF
 static __device__ unsigned long long g_phase[kPhaseSlots];
 #define PH_T(v) const unsigned long long v = __builtin_amdgcn_s_memtime()
@@ -1810,6 +1810,60 @@ __device__ __forceinline__ void row_inv_fwd(const Geo& G, const Part& D, cd* spe
       }
       wave_sync();
       cd* Y = fft_any(in2, Z, G.fq, false, lane, 64, WaveSync());
+      for (int k = lane; k < G.Qh; k += 64) {
+        cd ak, bk;
+        r2c_split(Y, G.Q, k, &ak, &bk);
+        store_pair(spec + (size_t)k * G.sld + r, two, pair_ok, ak, bk);
+      }
+      wave_sync();
+    }
+  }
+}
+
+// row_inv_fwd2: row_inv_fwd for per-wave plans with row_inv2's operand
+// batches: `ld(r, j)` loads a pixel's operands JCH columns at a time (the first
+// batch before the inverse FFT), `cp(r, j, value, ld(r, j))` consumes the
+// output pixel and returns the next convolution's input pixel.  The pixels
+// reach cp in row_inv2's order (per lane: columns ascending, row r before
+// r + 1) and the forward half is row_fwd2's (same zero padding, FFT and
+// r2c_split), so sums and spectra have the bits of the two separate passes.
+// Both transform buffers are busy until the forward FFT: the next pair's
+// spectrum is gathered through registers, not staged ahead.
+template <int JCH = kJCH, bool COMP = true, class LD, class CP>
+__device__ __forceinline__ void row_inv_fwd2(const Geo& G, const Part& D, cd* spec, cd* lds,
+                                             LD&& ld, CP&& cp) {
+  using V = decltype(ld(0, 0));
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const bool pair_ok = (G.sld & 1) == 0;
+  if (w < G.nfw) {
+    cd* a = lds + w * 2 * G.lpad;
+    cd* b = a + G.lpad;
+    for (int r = 2 * (D.gw0 + w); r < G.H; r += 2 * D.gws) {
+      const bool two = (r + 1) < G.H;
+      gather_pair(G, spec, G.sld, r, two, a, lane);
+      V v0[JCH], v1[JCH];
+      load_rows<JCH>(ld, r, two, 0, lane, G.W, v0, v1);
+      wave_sync();
+      cd* Z = fft_any<COMP>(a, b, G.fq, true, lane, 64, WaveSync());
+      cd* in2 = (Z == a) ? b : a;
+      for (int j0 = 0; j0 < G.Q; j0 += 64 * JCH) {
+        if (j0 > 0 && j0 < G.W) load_rows<JCH>(ld, r, two, j0, lane, G.W, v0, v1);
+#pragma unroll
+        for (int u = 0; u < JCH; ++u) {
+          const int j = j0 + 64 * u + lane;
+          if (j < G.Q) {
+            double va = 0.0, vb = 0.0;
+            if (j < G.W) {
+              const cd z = Z[j];
+              va = cp(r, j, z.x, v0[u]);
+              if (two) vb = cp(r + 1, j, z.y, v1[u]);
+            }
+            in2[j] = cmk(va, vb);
+          }
+        }
+      }
+      wave_sync();
+      cd* Y = fft_any<COMP>(in2, Z, G.fq, false, lane, 64, WaveSync());
       for (int k = lane; k < G.Qh; k += 64) {
         cd ak, bk;
         r2c_split(Y, G.Q, k, &ak, &bk);

@@ -28,6 +28,10 @@ struct ImgState {
   // raw counts stored in f32, gn_s = raw (scale_data 0/2); 2 = gn_s = raw / sc.
   // gfill is the null-pixel value vmin*eps^2 (sgp.py:202-204).
   int g32;
+  // which of the two x_tf / pw buffer pairs is current (slot_bufs): a line
+  // search that accepts its speculative fused pass (ls_phase) flips it.  It
+  // fills the padding before gfill: the size of the state does not change.
+  int par_tf;
   double gfill;
   double Valpha[32];
   double Fold[32];
@@ -88,6 +92,11 @@ struct SolveArgs {
                         // (status bit 4); 2^26 unless BSGP_SPIN_LIMIT says otherwise (tests)
   int fold_setup;       // persistent solver, slot order: every image's setup is the first
                         // task of its chain inside k_persist (no k_setup launch)
+  int ls_predict;       // persistent solver's line search: pass 1 does only what the predicted
+                        // outcome needs (ls_phase).  0: never; 1 (default): an accept after an
+                        // accepted lam = 1; 2 / 3: always an accept / a stagnation (tests);
+                        // 4: as 1, and a stagnation after a tiny step; 5: stagnations only
+                        // (both measured slower than 1 on C3).  BSGP_LS_PREDICT
 };
 
 hipError_t launch_setup(const SolveArgs& a, size_t lds, hipStream_t s);

@@ -190,11 +190,12 @@ struct Bufs {
   V *xa, *xb, *ga, *gb, *xtf, *dtf;
   V* pw;  // den^(beta-1) at the current x_tf (beta objective): reused by the
           // gradient (k_bb) and the next line search's series moments
+  V *xtf2, *pw2;  // the other x_tf / pw pair (ImgState::par_tf): free for a speculative accept
   cd* spec;
 };
 
 template <class V>
-__device__ __forceinline__ Bufs<V> slot_bufs(const SolveArgs& A, int img, int par) {
+__device__ __forceinline__ Bufs<V> slot_bufs(const SolveArgs& A, int img, int par, int par_tf = 0) {
   Bufs<V> b;
   double* ws = A.ws + (size_t)img * A.slot_stride;
   const size_t v = A.vec_stride;
@@ -209,9 +210,12 @@ __device__ __forceinline__ Bufs<V> slot_bufs(const SolveArgs& A, int img, int pa
   b.xb = par ? x0 : x1;
   b.ga = par ? g1 : g0;
   b.gb = par ? g0 : g1;
-  b.xtf = vb + 4 * v;
+  V* sp = reinterpret_cast<V*>(ws + A.slot_stride - 2 * v);  // the slot's last two vectors
+  b.xtf = par_tf ? sp : vb + 4 * v;
+  b.xtf2 = par_tf ? vb + 4 * v : sp;
   b.dtf = vb + 5 * v;
-  b.pw = vb + 6 * v;
+  b.pw = par_tf ? sp + v : vb + 6 * v;
+  b.pw2 = par_tf ? vb + 6 * v : sp + v;
   b.spec = reinterpret_cast<cd*>(ws + A.spec_off);
   return b;
 }
@@ -629,6 +633,7 @@ __device__ __forceinline__ void setup_phase(const SolveArgs& A, int img) {
     for (int k = 0; k < P.M_alpha; ++k) st.Valpha[k] = P.alpha_max;
     for (int k = 0; k < P.M; ++k) st.Fold[k] = -1e30;
     st.par = 0;
+    st.par_tf = 0;
     st.Xones = P.init_recon == 0;  // X = ones until the first BB update (sgp.py:279-280)
     st.stop = 0;
     st.iter = 1;
@@ -654,6 +659,7 @@ __device__ __forceinline__ void setup_phase(const SolveArgs& A, int img) {
     st.init_lr = P.lr;
     st.beta = beta0;
     st.konst = fsum[0];
+    st.lam = 1.0;  // no step yet: the line search's predictor reads it (ls_phase)
     st.g32 = g32;
     st.gfill = fill;
     if (!(ymin < INFINITY)) {
@@ -946,7 +952,7 @@ __device__ __forceinline__ void dir_phase(const SolveArgs& A, int img) {
   const int N = G.H * G.W;
   const int npair = (N + 1) / 2;
   const bool odd = (N & 1) != 0;
-  Bufs<V> B = slot_bufs<V>(A, img, st.par);
+  Bufs<V> B = slot_bufs<V>(A, img, st.par, st.par_tf);
   Dir D = make_dir(A, st);
   const double flux = st.flux;
   int evals = 0;
@@ -1062,7 +1068,10 @@ __global__ void __launch_bounds__(kBlock) BSGP_COL_ATTR k_col(SolveArgs A, int t
 // sgp.py:326-349 / 774-801: K trial lambdas per pass over (x_tf, d_tf, gn);
 // the first pass is fused into the inverse row transforms that produce d_tf.
 // Then x_tf += lam*d_tf and the row transforms of AT's input w.
-template <int K, int MODE, bool ADAPT, bool COOP, class V, bool SB = false>
+// PRED: the build carries the outcome prediction (below; the persistent
+// solver's).  It never changes a bit of the result, so builds with and
+// without it stay bitwise equal.
+template <int K, int MODE, bool ADAPT, bool COOP, class V, bool SB = false, bool PRED = false>
 __device__ __forceinline__ void ls_phase(const SolveArgs& A, int img) {
   // first pass (fused into the inverse rows of A(d)): one trial lambda = 1,
   // which is where most non-stagnating iterations accept; later passes
@@ -1083,7 +1092,7 @@ __device__ __forceinline__ void ls_phase(const SolveArgs& A, int img) {
   const bool bmap = SB ? false : P.bkg_is_map != 0;
   const double lr_st = st.lr;
   constexpr bool adapt = ADAPT;  // adaptive beta (sgp.py:798-800): K == 1, runtime mode
-  Bufs<V> B = slot_bufs<V>(A, img, st.par);
+  Bufs<V> B = slot_bufs<V>(A, img, st.par, st.par_tf);
   const double bks_scalar = st.bks_scalar;
   const double flux = st.flux;
   const double gd = st.gd;
@@ -1175,14 +1184,148 @@ __device__ __forceinline__ void ls_phase(const SolveArgs& A, int img) {
   // instead of a direct pass over the image.  Both sums come from the same
   // per-pixel arithmetic as a direct pass's (x0 + lam d_tf), summed in the
   // pass's own order.
-  const bool k2 = BSGP_LS1_K2 && !COOP && series;
+  // Prediction (SolveArgs::ls_predict; per-wave float64 builds, fixed beta
+  // with the series, one-workgroup images): a search almost always ends like
+  // the image's previous one, so pass 1 sums only what that outcome needs.
+  //  * accept (the last step was lam = 1): pass 1 becomes the speculative
+  //    fused pass below: the first trial's sums only (no moments, no u =
+  //    d_tf / a, no pw operand, no second trial), and the accept's work on the
+  //    same registers: x_tf + d_tf and den^(b-1) go to the slot's other
+  //    x_tf / pw pair and the rows of w are transformed in place of A(d)'s.
+  //    If the first trial passes, the pair becomes current (ImgState::par_tf)
+  //    and AT's column pass follows at once; if not, the current pair is
+  //    untouched, ls_replay supplies the moments and the search goes on (its
+  //    accept pass rewrites every row of the spectrum).
+  //  * stagnate (the last step was below kLsStagLam): the second trial will
+  //    come from the closed form, so its direct sums are skipped.
+  // A prediction only selects which route computes the sums.  Where the search
+  // then needs one that was left out, ls_replay below sums it over the stored
+  // (x_tf, d_tf, gn, pw) with pass 1's wave, row and lane assignment: every
+  // value accumulates the same terms in the same order per lane and goes
+  // through the same block reduction (each value's tree is its own), so it has
+  // the bits pass 1 would have produced.
+  constexpr bool kPredBuild = PRED && BSGP_LS1_K2 && !COOP && !ADAPT &&
+                              (MODE == 3 || MODE == 4) && sizeof(V) == 8;
+  constexpr double kLsStagLam = 1e-4;  // (tools/ls_predict_replay.py)
+  int pred = 0;                        // 0: none (the full pass 1), 1: accept, 2: stagnate
+  if constexpr (kPredBuild) {
+    if (series && tm.T == 1 && A.ls_predict != 0) {
+      const double ll = st.lam;
+      const int lp = A.ls_predict;
+      pred = lp == 2 ? 1 : lp == 3 ? 2 : ll == 1.0 ? (lp == 5 ? 0 : 1) : ll < kLsStagLam ? (lp >= 4 ? 2 : 0) : 0;
+    }
+  }
+  const bool k2 = BSGP_LS1_K2 && !COOP && series && pred == 0;
   const double lam2 = lam * P.beta;
   double f2 = NAN;     // the second trial's objective from pass 1
   bool have2 = false;  // f2 holds the next trial's objective
+  constexpr int O2 = 4 + 2 * (MS + 1);
+  constexpr int N1 = O2 + ((BSGP_LS1_K2 && !COOP) ? 2 : 0);  // lam=1 sums, const, dDiv/dbeta, P_m, Q_m, lam=beta sums
+  // The sums a prediction left out of pass 1 (with_mom: the moments and max|u|
+  // as well as the second trial's sums); not a pass of ls_passes.
+  auto ls_replay = [&](bool with_mom) __attribute__((always_inline)) {
+    if constexpr (kPredBuild) {
+      PH_T(tr0);
+      double t1[N1];
+#pragma unroll
+      for (int k = 0; k < N1; ++k) t1[k] = 0.0;
+      double umax = 0.0;
+      const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+      if (w < G.nfw) {
+        for (int r = 2 * (Pt.gw0 + w); r < G.H; r += 2 * Pt.gws) {
+          const int nr = (r + 1) < G.H ? 2 : 1;
+          for (int j = lane; j < G.W; j += 64) {
+            for (int rr = 0; rr < nr; ++rr) {  // pass 1's order: (r, j), then (r + 1, j)
+              const int i = (r + rr) * G.W + j;
+              const double x0 = B.xtf[i];
+              const double v = B.dtf[i];  // float64 storage: the value pass 1 had in registers
+              const double g = gdec(g_raw(g32, B.gns, i));
+              const double bkv = opt_ld(bmap, B.bks, i, bks_scalar);
+              if (with_mom) {
+                const double a = x0 + bkv;
+                const double u = v / a;
+                const double p0 = B.pw[i];
+                const double A0 = a * p0, B0 = (MODE == 4 ? (double)(obj.c2f * (float)g) : g) * p0;
+                double um = 1.0;
+#pragma unroll
+                for (int m = 0; m <= MS; ++m) {
+                  t1[4 + m] += A0 * um;
+                  t1[4 + MS + 1 + m] += B0 * um;
+                  um *= u;
+                }
+                const double au = fabs(u);
+                umax = (au > umax || au != au || !(a > 0)) ? (a > 0 ? au : INFINITY) : umax;
+              }
+              const double x2 = x0 + lam2 * v;
+              obj.template terms_m<MODE>(x2, x2 + bkv, g, &t1[O2]);
+            }
+          }
+        }
+      }
+      team_sum_max<N1>(t1, umax, red, tm);
+      if (with_mom) {
+        rho = umax;
+        if (threadIdx.x == 0) {
+          for (int m = 0; m <= MS; ++m) {
+            ser[m] = t1[4 + m];
+            ser[MS + 1 + m] = t1[4 + MS + 1 + m];
+          }
+        }
+      }
+      f2 = obj.combine(konst, t1[O2], t1[O2 + 1], flux, (double)N);
+      have2 = true;
+      PH_ADD(34, tr0);
+    }
+  };
+  bool spec_acc = false;  // the speculative pass was accepted: no accept pass
+  if constexpr (kPredBuild) {
+    if (pred == 1) {
+      double ts[2] = {0.0, 0.0};
+      const double bm1s = obj.beta - 1;
+      V* const xs = B.xtf2;
+      V* const ps = B.pw2;
+      struct SpIn {
+        double x0, g, bkv;
+      };
+      row_inv_fwd2<kLs1Jch, kLsComp>(
+          G, Pt, B.spec, lds,
+          [&](int r, int j) {
+            const int i = r * G.W + j;
+            SpIn q;
+            q.x0 = B.xtf[i];
+            q.g = g_raw(g32, B.gns, i);
+            q.bkv = opt_ld(bmap, B.bks, i, bks_scalar);
+            return q;
+          },
+          [&](int r, int j, double v, const SpIn& q) {
+            const int i = r * G.W + j;
+            B.dtf[i] = v;
+            const double g = gdec(q.g);
+            const double xt = q.x0 + lam * v;
+            const double den = xt + q.bkv;
+            const double p = fpow(den, bm1s);  // terms_m's power and the accept's
+            ts[0] += obj.c1 * (den * p);
+            ts[1] += (MODE == 4 ? (double)(obj.c2f * (float)g) : obj.c2 * g) * p;
+            xs[i] = xt;
+            ps[i] = p;
+            return g * (p / den);
+          });
+      team_sum<2>(ts, red, tm);
+      PH_ADD(37, tk0);
+      ++passes;
+      ++nls;
+      const double f1 = obj.combine(konst, ts[0], ts[1], flux, (double)N);
+      if (f1 <= fr + P.gamma * lam * gd || lam < 1e-12) {
+        f_acc = f1;
+        accepted = true;
+        spec_acc = true;
+      } else {
+        lam = lam * P.beta;
+      }
+    }
+  }
   // ---- pass 1, fused into the inverse rows that produce d_tf: lam = 1 direct
-  {
-    constexpr int O2 = 4 + 2 * (MS + 1);
-    constexpr int N1 = O2 + ((BSGP_LS1_K2 && !COOP) ? 2 : 0);  // lam=1 sums, const, dDiv/dbeta, P_m, Q_m, lam=beta sums
+  if (pred != 1) {
     double t1[N1];
 #pragma unroll
     for (int k = 0; k < N1; ++k) t1[k] = 0.0;
@@ -1271,9 +1414,22 @@ __device__ __forceinline__ void ls_phase(const SolveArgs& A, int img) {
       }
     }
   }
+#ifdef BSGP_PHASE_PROF
+  // (prediction counters: iterations per prediction, then those it missed)
+  if (threadIdx.x == 0 && pred) atomicAdd(&g_phase[pred == 1 ? 32 : 33], 1ull);
+#endif
+  // a predicted accept whose first trial failed: the moments, max|u| and the
+  // second trial's sums after all
+  if (pred == 1 && !accepted) {
+    ls_replay(true);
+#ifdef BSGP_PHASE_PROF
+    if (threadIdx.x == 0) atomicAdd(&g_phase[35], 1ull);
+#endif
+  }
+  const bool have_mom = !spec_acc;  // ser[] holds this iteration's moments
   // binomial coefficients of the series (and, for the tail bound, the
   // scaled leading terms |binom(., MS+1)| P_MS / P_0 of both series)
-  if (series && threadIdx.x == 0) {
+  if (series && have_mom && threadIdx.x == 0) {
     double c0 = 1.0, c1 = 1.0;
     ser[2 * (MS + 1)] = 1.0;
     ser[3 * (MS + 1)] = 1.0;
@@ -1303,6 +1459,13 @@ __device__ __forceinline__ void ls_phase(const SolveArgs& A, int img) {
     return l7 * rho * tail_c / (1.0 - lu) <= kSeriesTail;
   };
   PH_T(tk1);
+  // a predicted stagnation whose second trial is outside the closed form
+  if (pred == 2 && !accepted && !series_ok(lam)) {
+    ls_replay(false);
+#ifdef BSGP_PHASE_PROF
+    if (threadIdx.x == 0) atomicAdd(&g_phase[36], 1ull);
+#endif
+  }
   while (!accepted) {
     if (have2 && !series_ok(lam)) {
       // the second trial, summed by pass 1 (f2 is NaN only if its sums are:
@@ -1460,39 +1623,41 @@ __device__ __forceinline__ void ls_phase(const SolveArgs& A, int img) {
   struct AcIn {
     double x, d, g, bkv, p0;
   };
-  row_fwd2<kLsAccJch, kLsAccPf, kLsComp, COOP, BSGP_LSACC_PIPE, 16>(
-      G, Pt, G.H, G.W, G.sld, B.spec, lds,
-      [&](int r, int j) {
-        const int i = r * G.W + j;
-        AcIn q;
-        q.x = B.xtf[i];
-        q.d = B.dtf[i];
-        q.g = g_raw(g32, B.gns, i);
-        q.bkv = opt_ld(bmap, B.bks, i, bks_scalar);
-        q.p0 = opt_ld(pw_series, B.pw, i, 0.0);
-        return q;
-      },
-      [&](int r, int j, const AcIn& q) {
-        const int i = r * G.W + j;
-        const double xt = q.x + lam_acc * q.d;
-        B.xtf[i] = xt;
-        const double den = xt + q.bkv;
-        const double g = gdec(q.g);
-        if (P.variant != BSGP_VARIANT_BETA) return g / den;  // KL: w = gn/den
-        double p;
-        if (pw_series) {
-          const double t = lam_acc * (q.d / (q.x + q.bkv));
-          // (1+t)^(b-1) = 1 + e1 t (1 + e2 t (1 + ... (1 + e6 t))), e_m = (b-m)/m
-          double h = 1.0;
-#pragma unroll
-          for (int m = MS; m >= 1; --m) h = fma(fma(obj.beta, 1.0 / m, -1.0) * t, h, 1.0);
-          p = q.p0 * h;
-        } else {
-          p = fpow(den, bm1);
-        }
-        B.pw[i] = p;
-        return g * (p / den);
-      });
+  if (!spec_acc) {
+    row_fwd2<kLsAccJch, kLsAccPf, kLsComp, COOP, BSGP_LSACC_PIPE, 16>(
+        G, Pt, G.H, G.W, G.sld, B.spec, lds,
+        [&](int r, int j) {
+          const int i = r * G.W + j;
+          AcIn q;
+          q.x = B.xtf[i];
+          q.d = B.dtf[i];
+          q.g = g_raw(g32, B.gns, i);
+          q.bkv = opt_ld(bmap, B.bks, i, bks_scalar);
+          q.p0 = opt_ld(pw_series, B.pw, i, 0.0);
+          return q;
+        },
+        [&](int r, int j, const AcIn& q) {
+          const int i = r * G.W + j;
+          const double xt = q.x + lam_acc * q.d;
+          B.xtf[i] = xt;
+          const double den = xt + q.bkv;
+          const double g = gdec(q.g);
+          if (P.variant != BSGP_VARIANT_BETA) return g / den;  // KL: w = gn/den
+          double p;
+          if (pw_series) {
+            const double t = lam_acc * (q.d / (q.x + q.bkv));
+            // (1+t)^(b-1) = 1 + e1 t (1 + e2 t (1 + ... (1 + e6 t))), e_m = (b-m)/m
+            double h = 1.0;
+  #pragma unroll
+            for (int m = MS; m >= 1; --m) h = fma(fma(obj.beta, 1.0 / m, -1.0) * t, h, 1.0);
+            p = q.p0 * h;
+          } else {
+            p = fpow(den, bm1);
+          }
+          B.pw[i] = p;
+          return g * (p / den);
+        });
+  }
   PH_ADD(6, tk2);
   if (A.fuse_col & 2) {  // AT's column pass follows here
     PH_T(tc0);
@@ -1512,6 +1677,7 @@ __device__ __forceinline__ void ls_phase(const SolveArgs& A, int img) {
     st.beta = obj.beta;
     st.konst = konst;
     st.lam = lam_acc;
+    if (spec_acc) st.par_tf ^= 1;
     st.E_ls += nls;
     st.ls_passes += passes;
     st.ls_series += series_evals;
@@ -1544,7 +1710,7 @@ __device__ __forceinline__ void bb_phase(const SolveArgs& A, int img) {
   const int N = G.H * G.W;
   const int tid = threadIdx.x;
   const bool beta_obj = P.variant == BSGP_VARIANT_BETA;
-  Bufs<V> B = slot_bufs<V>(A, img, st.par);
+  Bufs<V> B = slot_bufs<V>(A, img, st.par, st.par_tf);
   Dir D = make_dir(A, st);
   const double lam = st.lam;
   const double lo = st.lo, hi = st.hi;
@@ -1788,7 +1954,7 @@ __device__ __attribute__((noinline)) void persist_col_a(ArgRef r, int img) {
 }
 template <int K, int MODE, bool ADAPT, bool COOP, class V, bool SB = false>
 __device__ __attribute__((noinline)) void persist_ls(ArgRef r, int img) {
-  ls_phase<K, MODE, ADAPT, COOP, V, SB>(args_of(r), __builtin_amdgcn_readfirstlane(img));
+  ls_phase<K, MODE, ADAPT, COOP, V, SB, true>(args_of(r), __builtin_amdgcn_readfirstlane(img));
 }
 template <bool COOP, class V>
 __device__ __attribute__((noinline)) void persist_bb(ArgRef r, int img) {
@@ -1953,7 +2119,7 @@ __global__ void __launch_bounds__(kBlock) k_persist_finalize(SolveArgs A) {
   ImgState& st = A.st[img];
   if (st.stop) return;
   const int N = A.g.H * A.g.W;
-  const Bufs<V> B = slot_bufs<V>(A, img, st.par);
+  const Bufs<V> B = slot_bufs<V>(A, img, st.par, st.par_tf);
   double* xo = A.out.x + (size_t)img * N;
   for (int i = threadIdx.x; i < N; i += kBlock) xo[i] = (double)B.xa[i] * st.sc;
   __syncthreads();
@@ -2033,7 +2199,7 @@ __global__ void __launch_bounds__(kBlock) k_track(SolveArgs A, int it) {
   const ImgState& st = A.st[img];
   if (it > 0 && st.iter != it + 1) return;  // iteration `it` did not run for this image
   const int N = A.g.H * A.g.W;
-  const Bufs<V> B = slot_bufs<V>(A, img, st.par);
+  const Bufs<V> B = slot_bufs<V>(A, img, st.par, st.par_tf);
   // k_bb flips `par` when the image goes on; a stopping image keeps it
   const V* x = (it == 0 || !st.stop) ? B.xa : B.xb;
   const int tid = threadIdx.x;

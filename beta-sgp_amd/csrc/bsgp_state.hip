@@ -9,7 +9,8 @@
 // header, the scalars and the history rows go through the first workgroup of
 // each image.  The slot layout is slot_bufs' (bsgp_kernels.hpp): gn and the
 // background map in float64 at 0 and vec_stride, then x0, x1, g0, g1, x_tf,
-// d_tf, pw in the storage type.
+// d_tf, pw in the storage type; after the spectrum the second x_tf / pw pair
+// (a record holds the current pair, a load fills the first).
 #include <hip/hip_runtime.h>
 
 #include "bsgp_internal.hpp"
@@ -44,14 +45,17 @@ __device__ __forceinline__ void st_locate(unsigned c, unsigned nV, unsigned nD, 
 __device__ __forceinline__ size_t st_rec_off(const StateLayout& L, int s) {
   return s == 0 ? L.x : s == 1 ? L.g : s == 2 ? L.xtf : s == 3 ? L.pw : s == 4 ? L.gn : L.bkg;
 }
-// byte offset of a section's vector inside a slot; buf picks x0/g0 or x1/g1
-__device__ __forceinline__ size_t st_slot_off(const StateArgs& S, int s, int buf) {
+// byte offset of a section's vector inside a slot; buf picks x0/g0 or x1/g1,
+// ptf the first x_tf / pw pair or the second (ImgState::par_tf: the slot's
+// last two vectors)
+__device__ __forceinline__ size_t st_slot_off(const StateArgs& S, int s, int buf, int ptf = 0) {
   const size_t v = S.vec_stride, vb = S.storage == BSGP_STORAGE_F32 ? 4 : 8;
   const size_t base = 2 * v * 8;
+  const size_t spare = (S.slot_stride - 2 * v) * 8;
   return s == 0   ? base + (size_t)buf * v * vb
          : s == 1 ? base + (size_t)(2 + buf) * v * vb
-         : s == 2 ? base + 4 * v * vb
-         : s == 3 ? base + 6 * v * vb
+         : s == 2 ? (ptf ? spare : base + 4 * v * vb)
+         : s == 3 ? (ptf ? spare + v * vb : base + 6 * v * vb)
          : s == 4 ? 0
                   : v * 8;
 }
@@ -119,7 +123,7 @@ __global__ void __launch_bounds__(kStBlock) k_state_save(StateArgs S) {
       int s;
       unsigned k;
       st_locate(c < total ? c : total - 1u, nV, nD, s, k);
-      w[u] = *reinterpret_cast<const uint4*>(slot + st_slot_off(S, s, buf) + (size_t)k * 16);
+      w[u] = *reinterpret_cast<const uint4*>(slot + st_slot_off(S, s, buf, st.par_tf) + (size_t)k * 16);
     }
 #pragma unroll
     for (int u = 0; u < kStU; ++u) {
@@ -295,6 +299,7 @@ __global__ void __launch_bounds__(kStBlock) k_state_load(StateArgs S) {
     }
   }
   st.par = 0;
+  st.par_tf = 0;  // the record's x_tf / pw went to the first pair
   st.Xones = h->Xones;
   st.stop = fin != 0;
   st.iter = done + 1;

@@ -10,7 +10,7 @@ B=/tmp/bsgp_build_$NAME; mkdir -p $B
 CF="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -mcode-object-version=5"
 OBJS=(); PIDS=()
 rm -f $B/*.o
-for f in bsgp_solver bsgp_solver_f32 bsgp_solver_c512 bsgp_persist bsgp_persist_f32 bsgp_persist_c512 bsgp_persist_c512_f32 bsgp_persist_app bsgp_api bsgp_tiles bsgp_psf; do
+for f in bsgp_solver bsgp_solver_f32 bsgp_solver_c512 bsgp_persist bsgp_persist_f32 bsgp_persist_c512 bsgp_persist_c512_f32 bsgp_persist_app bsgp_api bsgp_tiles bsgp_psf bsgp_state bsgp_background bsgp_segment; do
   /opt/rocm/bin/hipcc $CF $FLAGS -I $SRC/include -c $SRC/beta-sgp_amd/csrc/$f.hip -o $B/$f.o &
   PIDS+=($!); OBJS+=($B/$f.o)
 done

@@ -30,7 +30,12 @@ SLOTS = {0: "k_dir projection", 1: "k_dir row pass", 2: "k_dir total", 3: "k_col
          22: "  dir rows: operand batches", 23: "  dir rows: FFT", 24: "  dir rows: stores",
          25: "  coop rows: spectrum gathers | ls1 red.: own waves", 26: "  coop rows: FFTs | ls1 red.: other members", 27: "  coop rows: operands",
          28: "  coop rows: spectrum stores", 29: "  coop cols: loads", 30: "  coop cols: FFT+TF+store",
-         31: "persistent: dequeue + wait for the previous iteration"}
+         31: "persistent: dequeue + wait for the previous iteration",
+         34: "k_ls replay of skipped sums", 37: "k_ls speculative fused pass"}
+# line-search prediction counters (events, not cycles): iterations per
+# prediction and the mispredicted ones among them (a replay pass each)
+COUNTS = {32: "predicted accept", 35: "  first trial failed (replay)",
+          33: "predicted stagnation", 36: "  second trial needed (replay)"}
 
 
 def main():
@@ -49,7 +54,7 @@ def main():
     bench.torch = torch
     L = _bsgp.lib()
     L.bsgp_phase_prof.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32]
-    buf = (ctypes.c_uint64 * 32)()
+    buf = (ctypes.c_uint64 * 40)()
     if args.config == "app375":  # one application subdivision (bench.py app375), automatic team
         img, psf, bk, akw, betas = bench.app375_inputs()
         gn = torch.from_numpy(np.asarray(img, dtype=np.float32).copy()).cuda()[None]
@@ -75,13 +80,15 @@ def main():
         kw = bench.solve_kwargs(args.maxit, None, args.streams, None, circular=cfg["circular"],
                                 persistent=args.persistent)
     sgp.sgp_betaDiv_batch(gn, psf, bkg, device_out=True, **kw)
-    _bsgp.check(L.bsgp_phase_prof(buf, 32, 1))  # reset after warm-up
+    _bsgp.check(L.bsgp_phase_prof(buf, 40, 1))  # reset after warm-up
     out = sgp.sgp_betaDiv_batch(gn, psf, bkg, device_out=True, **kw)
-    _bsgp.check(L.bsgp_phase_prof(buf, 32, 1))
+    _bsgp.check(L.bsgp_phase_prof(buf, 40, 1))
     n = float(out["iters"].sum().item()) * float(out["counters"][0, 5].item())  # x team size
     for k, name in SLOTS.items():
         print(f"{name:32s} {buf[k] / n:12.0f} cycles per image-iteration"
               + (" (2 launches)" if k == 3 else ""))
+    for k, name in COUNTS.items():
+        print(f"{name:32s} {buf[k]:12d} image-iterations ({100.0 * buf[k] / n:5.1f} %)")
 
 
 if __name__ == "__main__":
