@@ -848,6 +848,95 @@ __device__ __forceinline__ double np_min2(double a, double b) {
 __device__ __forceinline__ double py_max2(double a, double b) { return (b > a) ? b : a; }
 __device__ __forceinline__ double py_min2(double a, double b) { return (b < a) ? b : a; }
 
+// -------------------------------------------------------------- cache policy
+// Stream policy of the per-wave passes: a bitmask template argument POL, one
+// bit per class of access; a set bit makes that class non-temporal (`nt`:
+// served by the L2, not kept in L1, first in line for eviction), so that the
+// stream-once traffic of a persistent workgroup does not push the reused data
+// (the transfer function, the projection's pixel lists) out of the L2.  POL = 0
+// is the plain code, access for access.  Never part of a policy: the TF loads
+// of col_conv, the pixel lists, load_tw_lds, ImgState and the counters, and
+// everything that crosses workgroups with sc1 accesses (done[], the ring, team
+// partials).  The arithmetic does not depend on POL.
+enum : unsigned {
+  kNtO16 = 1u,  // 16-byte operand loads: ld2 of the direction's rows and bb_phase
+  kNtO8 = 2u,   // 8-byte operand loads of the line search's passes (gn included)
+  kNtW = 4u,    // operand stores: x, g, x_tf, d_tf, pw
+  kNtSR = 8u,   // row-side spectrum: gather_pair, stage_pair (LDS-DMA), store_pair
+  kNtSC = 16u,  // column-side spectrum: col_conv's column loads and stores
+  kNtPJ = 32u,  // the projection's passes over (x, g) (measured apart from kNtO8)
+};
+
+typedef double nt_d2 __attribute__((ext_vector_type(2)));
+typedef nt_d2 nt_d2_a8 __attribute__((aligned(8)));
+typedef double nt_d_a4 __attribute__((aligned(4)));
+// (ptr: the type the access goes through, val: the value it moves)
+template <int BYTES, int ALIGN>
+struct NtRep;
+template <int ALIGN>
+struct NtRep<4, ALIGN> {
+  typedef float ptr;
+  typedef float val;
+};
+template <>
+struct NtRep<8, 4> {
+  typedef nt_d_a4 ptr;
+  typedef double val;
+};
+template <>
+struct NtRep<8, 8> {
+  typedef double ptr;
+  typedef double val;
+};
+template <>
+struct NtRep<16, 8> {
+  typedef nt_d2_a8 ptr;
+  typedef nt_d2 val;
+};
+template <>
+struct NtRep<16, 16> {
+  typedef nt_d2 ptr;
+  typedef nt_d2 val;
+};
+
+// Load / store one T (4, 8 or a multiple of 16 bytes) with the policy bit NT:
+// plain when off; when on, the same bits through a type the non-temporal
+// builtins take (global_load/store_dword, _dwordx2, _dwordx4 ... nt).
+template <bool NT, class T, int ALIGN = (alignof(T) < 16 ? (int)alignof(T) : 16)>
+__device__ __forceinline__ T ldp(const T* p) {
+  if constexpr (!NT) {
+    return *p;
+  } else {
+    constexpr int B = sizeof(T) <= 16 ? (int)sizeof(T) : 16;
+    static_assert(sizeof(T) % B == 0, "4, 8 or whole 16-byte pieces");
+    typedef NtRep<B, (B < ALIGN ? B : ALIGN)> Rep;
+    typedef typename Rep::ptr R;
+    typename Rep::val r[sizeof(T) / B];
+#pragma unroll
+    for (int n = 0; n < (int)(sizeof(T) / B); ++n)
+      r[n] = __builtin_nontemporal_load(reinterpret_cast<const R*>(p) + n);
+    T v;
+    __builtin_memcpy(&v, r, sizeof(T));
+    return v;
+  }
+}
+template <bool NT, class T, int ALIGN = (alignof(T) < 16 ? (int)alignof(T) : 16)>
+__device__ __forceinline__ void stp(T* p, const T& v) {
+  if constexpr (!NT) {
+    *p = v;
+  } else {
+    constexpr int B = sizeof(T) <= 16 ? (int)sizeof(T) : 16;
+    static_assert(sizeof(T) % B == 0, "4, 8 or whole 16-byte pieces");
+    typedef NtRep<B, (B < ALIGN ? B : ALIGN)> Rep;
+    typedef typename Rep::ptr R;
+    typename Rep::val r[sizeof(T) / B];
+    __builtin_memcpy(r, &v, sizeof(T));
+#pragma unroll
+    for (int n = 0; n < (int)(sizeof(T) / B); ++n)
+      __builtin_nontemporal_store(r[n], reinterpret_cast<R*>(p) + n);
+  }
+}
+
 // --------------------------------------------------------------- conv passes
 // Spectrum scratch of one image is COLUMN-major: spec[k * ld + p] for stored
 // column k < Qh and row p < ld (ld = H: the zero-filled rows H..P-1 of the
@@ -859,15 +948,17 @@ struct alignas(32) CPair {
   cd a, b;
 };
 
+template <unsigned POL = 0>
 __device__ __forceinline__ void store_pair(cd* col, bool two, bool pair_ok, cd ak, cd bk) {
+  constexpr bool NT = (POL & kNtSR) != 0;
   if (two && pair_ok) {
     CPair v;
     v.a = ak;
     v.b = bk;
-    *reinterpret_cast<CPair*>(col) = v;
+    stp<NT>(reinterpret_cast<CPair*>(col), v);
   } else {
-    col[0] = ak;
-    if (two) col[1] = bk;
+    stp<NT>(col, ak);
+    if (two) stp<NT>(col + 1, bk);
   }
 }
 
@@ -1509,7 +1600,8 @@ __device__ __forceinline__ void coop_col_conv(const Geo& G, const Part& D, cd* s
 // ld2: the pass's wide loader, if it has one (Two<V> above): rows of even
 // length take it, odd lengths and cooperative plans keep ld.
 template <int JCH = kJCH, bool PF = false, bool COMP = true, bool COOP = false,
-          bool PIPE = false, int PHS = -1, class LD, class MK, class LD2 = NoWide>
+          bool PIPE = false, int PHS = -1, unsigned POL = 0, class LD, class MK,
+          class LD2 = NoWide>
 __device__ __forceinline__ void row_fwd2(const Geo& G, const Part& D, int nrows, int ncols,
                                          int ldim, cd* spec, cd* lds, LD&& ld, MK&& mk,
                                          LD2&& ld2 = LD2{}) {
@@ -1589,7 +1681,7 @@ __device__ __forceinline__ void row_fwd2(const Geo& G, const Part& D, int nrows,
       for (int k = lane; k < G.Qh; k += 64) {
         cd ak, bk;
         r2c_split(Z, G.Q, k, &ak, &bk);
-        store_pair(spec + (size_t)k * ldim + r, two, pair_ok, ak, bk);
+        store_pair<POL>(spec + (size_t)k * ldim + r, two, pair_ok, ak, bk);
       }
       wave_sync();
       PH_SUB(PHS + 2, tph);
@@ -1616,16 +1708,18 @@ __device__ __forceinline__ void row_fwd(const Geo& G, const Part& D, int nrows, 
 
 // Rebuild the full-length spectrum of row pair (r, r+1) into `a`: each
 // stored column k < Qh is loaded once and yields Z_k and Z_{Q-k}.
+template <unsigned POL = 0>
 __device__ __forceinline__ void gather_pair(const Geo& G, const cd* spec, int ld, int r, bool two,
                                             cd* a, int lane) {
+  constexpr bool NT = (POL & kNtSR) != 0;
   for (int k0 = lane; k0 < G.Qh; k0 += 64 * kGCH) {
     cd A[kGCH], B[kGCH];
 #pragma unroll
     for (int u = 0; u < kGCH; ++u) {  // clamped, branch-free
       const int k = min(k0 + 64 * u, G.Qh - 1);
       const cd* col = spec + (size_t)k * ld + r;
-      A[u] = col[0];
-      const cd bk = col[two ? 1 : 0];
+      A[u] = ldp<NT>(col);
+      const cd bk = ldp<NT>(col + (two ? 1 : 0));
       B[u] = two ? bk : cmk(0.0, 0.0);
     }
 #pragma unroll
@@ -1647,13 +1741,15 @@ __device__ __forceinline__ void gather_pair(const Geo& G, const cd* spec, int ld
 // per row touched 64 and asked for every line twice.  Needs lpad >= 2*Qh.
 typedef __attribute__((address_space(3))) void lds_void_t;
 typedef __attribute__((address_space(1))) void gbl_void_t;
+template <unsigned POL = 0>
 __device__ __forceinline__ void stage_pair(const Geo& G, const cd* spec, int ld, int r, bool two,
                                            cd* F, int lane) {
+  constexpr int kAux = (POL & kNtSR) ? 2 : 0;  // aux bit 1: nt
   for (int k0 = 0; k0 < G.Qh; k0 += 32) {
     const int k = k0 + (lane >> 1);
     if (k < G.Qh) {  // (without a row r + 1 the odd lanes fetch row r again, unused)
       const cd* col = spec + (size_t)k * ld + r + (two ? (lane & 1) : 0);
-      __builtin_amdgcn_global_load_lds((gbl_void_t*)col, (lds_void_t*)(F + 2 * k0), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((gbl_void_t*)col, (lds_void_t*)(F + 2 * k0), 16, 0, kAux);
     }
   }
 }
@@ -1678,7 +1774,8 @@ __device__ __forceinline__ void unpack_pair(const Geo& G, const cd* F, bool two,
 // PIPE: as row_fwd2 (batch j0 + 64*JCH in flight while batch j0 is consumed).
 // ld2: as row_fwd2.
 template <bool PRE, int JCH = kJCH, bool COMP = true, bool COOP = false,
-          bool PIPE = false, int PHS = -1, class LD, class USE, class LD2 = NoWide>
+          bool PIPE = false, int PHS = -1, unsigned POL = 0, class LD, class USE,
+          class LD2 = NoWide>
 __device__ __forceinline__ void row_inv2(const Geo& G, const Part& D, const cd* spec, cd* lds,
                                          LD&& ld, USE&& use, LD2&& ld2 = LD2{}) {
   if constexpr (COOP) {
@@ -1702,7 +1799,7 @@ __device__ __forceinline__ void row_inv2(const Geo& G, const Part& D, const cd* 
     cd* other = in + G.lpad;
     int r = 2 * (D.gw0 + w);
     PH_SUB_T(tph);
-    if (r < G.H) gather_pair(G, spec, G.sld, r, (r + 1) < G.H, in, lane);
+    if (r < G.H) gather_pair<POL>(G, spec, G.sld, r, (r + 1) < G.H, in, lane);
     for (; r < G.H; r += 2 * D.gws) {
       const bool two = (r + 1) < G.H;
       V v0[JCH], v1[JCH];
@@ -1714,7 +1811,7 @@ __device__ __forceinline__ void row_inv2(const Geo& G, const Part& D, const cd* 
       cd* F = (Z == in) ? other : in;
       const int rn = r + 2 * D.gws;
       const bool next = rn < G.H, two_n = (rn + 1) < G.H;
-      if (next) stage_pair(G, spec, G.sld, rn, two_n, F, lane);
+      if (next) stage_pair<POL>(G, spec, G.sld, rn, two_n, F, lane);
       auto eat = [&](int j0, const V (&w0)[JCH], const V (&w1)[JCH]) __attribute__((always_inline)) {
 #pragma unroll
         for (int u = 0; u < JCH; ++u) {
@@ -1829,7 +1926,7 @@ __device__ __forceinline__ void row_inv_fwd(const Geo& G, const Part& D, cd* spe
 // r2c_split), so sums and spectra have the bits of the two separate passes.
 // Both transform buffers are busy until the forward FFT: the next pair's
 // spectrum is gathered through registers, not staged ahead.
-template <int JCH = kJCH, bool COMP = true, class LD, class CP>
+template <int JCH = kJCH, bool COMP = true, unsigned POL = 0, class LD, class CP>
 __device__ __forceinline__ void row_inv_fwd2(const Geo& G, const Part& D, cd* spec, cd* lds,
                                              LD&& ld, CP&& cp) {
   using V = decltype(ld(0, 0));
@@ -1840,7 +1937,7 @@ __device__ __forceinline__ void row_inv_fwd2(const Geo& G, const Part& D, cd* sp
     cd* b = a + G.lpad;
     for (int r = 2 * (D.gw0 + w); r < G.H; r += 2 * D.gws) {
       const bool two = (r + 1) < G.H;
-      gather_pair(G, spec, G.sld, r, two, a, lane);
+      gather_pair<POL>(G, spec, G.sld, r, two, a, lane);
       V v0[JCH], v1[JCH];
       load_rows<JCH>(ld, r, two, 0, lane, G.W, v0, v1);
       wave_sync();
@@ -1867,7 +1964,7 @@ __device__ __forceinline__ void row_inv_fwd2(const Geo& G, const Part& D, cd* sp
       for (int k = lane; k < G.Qh; k += 64) {
         cd ak, bk;
         r2c_split(Y, G.Q, k, &ak, &bk);
-        store_pair(spec + (size_t)k * G.sld + r, two, pair_ok, ak, bk);
+        store_pair<POL>(spec + (size_t)k * G.sld + r, two, pair_ok, ak, bk);
       }
       wave_sync();
     }
@@ -1881,9 +1978,11 @@ __device__ __forceinline__ void row_inv_fwd2(const Geo& G, const Part& D, cd* sp
 // The TF is loaded after the forward FFT: measured on C3 (A/B), that keeps
 // k_col at 111 VGPRs (4 waves/SIMD) and runs 8 % faster than batching its
 // loads with the column's.
-template <bool COOP = false>
+// POL & kNtSC: the column's loads and stores are non-temporal; the TF's never.
+template <bool COOP = false, unsigned POL = 0>
 __device__ __forceinline__ void col_conv(const Geo& G, const Part& D, cd* spec, const cd* tf,
                                          cd* lds) {
+  constexpr bool NT = (POL & kNtSC) != 0;
   if constexpr (COOP) {
     coop_col_conv(G, D, spec, tf, lds);
     return;
@@ -1894,7 +1993,11 @@ __device__ __forceinline__ void col_conv(const Geo& G, const Part& D, cd* spec, 
     cd* b = a + G.lpad;
     for (int k = D.gw0 + w; k < G.Qh; k += D.gws) {
       cd* col = spec + (size_t)k * G.sld;
+#ifdef BSGP_TF_ONECOL  // diagnostic (traffic and time only): every column takes TF column 0
+      const cd* t = tf;
+#else
       const cd* t = tf + (size_t)k * G.P;
+#endif
       for (int p0 = 0; p0 < G.P; p0 += 64 * kPCH) {
         cd cv[kPCH];
 #pragma unroll
@@ -1902,7 +2005,7 @@ __device__ __forceinline__ void col_conv(const Geo& G, const Part& D, cd* spec, 
           // branch-free (a conditional load ends in a join that waits for every
           // load in flight): clamp the index, select after the load
           const int p = p0 + lane + 64 * u;
-          const cd c = col[min(p, G.H - 1)];
+          const cd c = ldp<NT>(col + min(p, G.H - 1));
           cv[u] = p < G.H ? c : cmk(0.0, 0.0);
         }
 #pragma unroll
@@ -1928,7 +2031,7 @@ __device__ __forceinline__ void col_conv(const Geo& G, const Part& D, cd* spec, 
       }
       wave_sync();
       cd* Y = fft_any(Z, (Z == a) ? b : a, G.fp, true, lane, 64, WaveSync());
-      for (int p = lane; p < G.H; p += 64) col[p] = Y[p];
+      for (int p = lane; p < G.H; p += 64) stp<NT>(col + p, Y[p]);
       wave_sync();
     }
   }

@@ -59,6 +59,13 @@ constexpr int kLs1Jch = 1;
 #ifndef BSGP_LS1_K2
 #define BSGP_LS1_K2 0
 #endif
+// Stream policy of the persistent solver's phases (bsgp_device.hpp, "cache
+// policy": a bitmask of kNt* classes made non-temporal).  Only k_persist's
+// phase functions take it; the phase kernels are always plain.  Each persistent
+// translation unit may set its own default before including this header.
+#ifndef BSGP_STREAM_NT
+#define BSGP_STREAM_NT 0
+#endif
 // closed-form line-search trials are evaluated kLsLanes at a time, one per
 // lane (ls_phase)
 constexpr int kLsLanes = 32;
@@ -135,12 +142,15 @@ __device__ __forceinline__ void stream2(const Part& D, int npair, LD&& ld, CP&& 
     stream_range<U>(p0, p0 + D.cp < npair ? p0 + D.cp : npair, ld, cp);
 }
 
+// (NT here and below: the access's stream-policy bit, bsgp_device.hpp)
+template <bool NT = false>
 __device__ __forceinline__ double2 ld2(const double* a, int p) {
-  return reinterpret_cast<const double2*>(a)[p];
+  return ldp<NT>(reinterpret_cast<const double2*>(a) + p);
 }
 // float32 storage (BSGP_STORAGE_F32): a pair of stored floats, widened
+template <bool NT = false>
 __device__ __forceinline__ double2 ld2(const float* a, int p) {
-  const float2 f = reinterpret_cast<const float2*>(a)[p];
+  const float2 f = ldp<NT>(reinterpret_cast<const float2*>(a) + p);
   return double2{(double)f.x, (double)f.y};
 }
 
@@ -150,30 +160,34 @@ __device__ __forceinline__ double2 ld2(const float* a, int p) {
 // its own pixel when the wave-uniform flag is on, element 0 of the same slot
 // vector (one cache line for the whole wave) when it is off; the value is
 // selected after the load.  Every slot vector exists in every plan.
-template <class T>
+template <bool NT = false, class T>
 __device__ __forceinline__ double opt_ld(bool on, const T* a, int i, double off) {
-  const double v = (double)a[on ? i : 0];
+  const double v = (double)ldp<NT>(a + (on ? i : 0));
   return on ? v : off;
 }
-template <class T>
+template <bool NT = false, class T>
 __device__ __forceinline__ double2 opt_ld2(bool on, const T* a, int p, double off) {
-  const double2 v = ld2(a, on ? p : 0);
+  const double2 v = ld2<NT>(a, on ? p : 0);
   return on ? v : double2{off, off};
 }
 // The observed-image operand in one 8-byte load for both layouts: compact
 // (ImgState::g32, the raw float32 gnf[i] in the low word) or float64 gns[i].
 // The compact array is the first half of the gns slot vector, so the word
 // after gnf[i] is in bounds.
+template <bool NT = false>
 __device__ __forceinline__ double g_raw(bool g32, const double* gns, int i) {
   const unsigned int* w = reinterpret_cast<const unsigned int*>(gns) + (g32 ? i : 2 * i);
+  if constexpr (NT) return ldp<true, double, 4>(reinterpret_cast<const double*>(w));
   unsigned long long u;
   __builtin_memcpy(&u, __builtin_assume_aligned(w, 4), 8);
   return __longlong_as_double((long long)u);
 }
 // Pixel pair p: compact = floats gnf[2p], gnf[2p+1] in the first 8 bytes
 // (16 bytes are read either way; the wave's lines are the same).
+template <bool NT = false>
 __device__ __forceinline__ double2 g_raw2(bool g32, const double* gns, int p) {
   const double* a = g32 ? gns + p : gns + 2 * p;  // gnf + 2p == (double*)gns + p
+  if constexpr (NT) return ldp<true, double2, 8>(reinterpret_cast<const double2*>(a));
   double2 v;
   __builtin_memcpy(&v, __builtin_assume_aligned(a, 8), 16);
   return v;
@@ -731,7 +745,7 @@ constexpr int kProjWidePx = 16;
 // evaluation reads no global memory; C4: 16 of up to 32 entries), the rest
 // in global memory (LL: compiled in; the persistent one-workgroup solver
 // keeps global lists).
-template <class V, bool LL>
+template <class V, bool LL, unsigned POL = 0>
 __device__ __forceinline__ ProjOut cached_projection(const SolveArgs& A, int img, const Part& Pt, Team& tm,
                                      const Dir& D, const Bufs<V>& B, double* red, cd* lds,
                                      double lam_prev, double flux, int npair, bool odd, int N,
@@ -817,8 +831,8 @@ __device__ __forceinline__ ProjOut cached_projection(const SolveArgs& A, int img
           struct Ld {
             double2 x, g;
           } v;
-          v.x = ld2(xa, p);
-          v.g = ld2(ga, p);
+          v.x = ld2<(POL & kNtPJ) != 0>(xa, p);
+          v.g = ld2<(POL & kNtPJ) != 0>(ga, p);
           return v;
         },
         [&](int p, const auto& v) {
@@ -940,8 +954,9 @@ __device__ __forceinline__ ProjOut cached_projection(const SolveArgs& A, int img
 // d.g, and the row transforms of d.
 // One image's phase (the kernel below, or the persistent solver's task): the
 // caller has checked st.stop and loaded the twiddles into LDS.
-template <bool COOP, class V, bool LL = true>
+template <bool COOP, class V, bool LL = true, unsigned POL = 0>
 __device__ __forceinline__ void dir_phase(const SolveArgs& A, int img) {
+  constexpr bool kO16 = (POL & kNtO16) != 0, kO8 = (POL & kNtO8) != 0;
   BSGP_LDS_VIEWS(A);
   ImgState& st = A.st[img];
   PH_T(tk0);
@@ -960,7 +975,7 @@ __device__ __forceinline__ void dir_phase(const SolveArgs& A, int img) {
   double lam_ratio = 0.0, kappa = 0.0;
   if (P.proj_type == 1 && A.plist != nullptr) {
     double first_lam = NAN;  // the search's first multiplier off the first pass
-    ProjOut po = cached_projection<V, LL>(A, img, Pt, tm, D, B, red, lds, st.lam_p, flux, npair,
+    ProjOut po = cached_projection<V, LL, POL>(A, img, Pt, tm, D, B, red, lds, st.lam_p, flux, npair,
                                           odd, N, ppass, plist_reads, st.lam_ratio, st.kappa,
                                           first_lam);
     D.lam_p = po.lam;
@@ -978,8 +993,8 @@ __device__ __forceinline__ void dir_phase(const SolveArgs& A, int img) {
             struct Ld {
               double2 x, g;
             } v;
-            v.x = ld2(xa, p);
-            v.g = ld2(ga, p);
+            v.x = ld2<(POL & kNtPJ) != 0>(xa, p);
+            v.g = ld2<(POL & kNtPJ) != 0>(ga, p);
             return v;
           },
           [&](int p, const auto& v) {
@@ -1002,11 +1017,11 @@ __device__ __forceinline__ void dir_phase(const SolveArgs& A, int img) {
   PH_ADD(0, tk0);
   PH_T(tk1);
   double gd[1] = {0.0};
-  row_fwd2<kDirJch, kDirPf, kDirComp, COOP, false, 22>(
+  row_fwd2<kDirJch, kDirPf, kDirComp, COOP, false, 22, POL>(
       G, Pt, G.H, G.W, G.sld, B.spec, lds,
       [&](int r, int j) {
         const int i = r * G.W + j;
-        return double2{B.xa[i], B.ga[i]};
+        return double2{(double)ldp<kO8>(B.xa + i), (double)ldp<kO8>(B.ga + i)};
       },
       [&](int, int, const double2& v) {
         const double d = D.d(v.x, v.y);
@@ -1015,7 +1030,7 @@ __device__ __forceinline__ void dir_phase(const SolveArgs& A, int img) {
       },
       [&](int r, int j) {
         const int p = (r * G.W + j) >> 1;
-        const double2 x = ld2(B.xa, p), g = ld2(B.ga, p);
+        const double2 x = ld2<kO16>(B.xa, p), g = ld2<kO16>(B.ga, p);
         return Two<double2>{double2{x.x, g.x}, double2{x.y, g.y}};
       });
   if (row_wide<COOP>(G)) gd[0] = split_undo(gd[0]);  // the partials back to their lanes
@@ -1071,8 +1086,10 @@ __global__ void __launch_bounds__(kBlock) BSGP_COL_ATTR k_col(SolveArgs A, int t
 // PRED: the build carries the outcome prediction (below; the persistent
 // solver's).  It never changes a bit of the result, so builds with and
 // without it stay bitwise equal.
-template <int K, int MODE, bool ADAPT, bool COOP, class V, bool SB = false, bool PRED = false>
+template <int K, int MODE, bool ADAPT, bool COOP, class V, bool SB = false, bool PRED = false,
+          unsigned POL = 0>
 __device__ __forceinline__ void ls_phase(const SolveArgs& A, int img) {
+  constexpr bool kO8 = (POL & kNtO8) != 0, kW = (POL & kNtW) != 0;
   // first pass (fused into the inverse rows of A(d)): one trial lambda = 1,
   // which is where most non-stagnating iterations accept; later passes
   // stream K trial lambdas each.
@@ -1237,14 +1254,14 @@ __device__ __forceinline__ void ls_phase(const SolveArgs& A, int img) {
           for (int j = lane; j < G.W; j += 64) {
             for (int rr = 0; rr < nr; ++rr) {  // pass 1's order: (r, j), then (r + 1, j)
               const int i = (r + rr) * G.W + j;
-              const double x0 = B.xtf[i];
-              const double v = B.dtf[i];  // float64 storage: the value pass 1 had in registers
-              const double g = gdec(g_raw(g32, B.gns, i));
-              const double bkv = opt_ld(bmap, B.bks, i, bks_scalar);
+              const double x0 = ldp<kO8>(B.xtf + i);
+              const double v = ldp<kO8>(B.dtf + i);  // float64 storage: the value pass 1 had in registers
+              const double g = gdec(g_raw<kO8>(g32, B.gns, i));
+              const double bkv = opt_ld<kO8>(bmap, B.bks, i, bks_scalar);
               if (with_mom) {
                 const double a = x0 + bkv;
                 const double u = v / a;
-                const double p0 = B.pw[i];
+                const double p0 = ldp<kO8>(B.pw + i);
                 const double A0 = a * p0, B0 = (MODE == 4 ? (double)(obj.c2f * (float)g) : g) * p0;
                 double um = 1.0;
 #pragma unroll
@@ -1287,27 +1304,27 @@ __device__ __forceinline__ void ls_phase(const SolveArgs& A, int img) {
       struct SpIn {
         double x0, g, bkv;
       };
-      row_inv_fwd2<kLs1Jch, kLsComp>(
+      row_inv_fwd2<kLs1Jch, kLsComp, POL>(
           G, Pt, B.spec, lds,
           [&](int r, int j) {
             const int i = r * G.W + j;
             SpIn q;
-            q.x0 = B.xtf[i];
-            q.g = g_raw(g32, B.gns, i);
-            q.bkv = opt_ld(bmap, B.bks, i, bks_scalar);
+            q.x0 = ldp<kO8>(B.xtf + i);
+            q.g = g_raw<kO8>(g32, B.gns, i);
+            q.bkv = opt_ld<kO8>(bmap, B.bks, i, bks_scalar);
             return q;
           },
           [&](int r, int j, double v, const SpIn& q) {
             const int i = r * G.W + j;
-            B.dtf[i] = v;
+            stp<kW>(B.dtf + i, (V)v);
             const double g = gdec(q.g);
             const double xt = q.x0 + lam * v;
             const double den = xt + q.bkv;
             const double p = fpow(den, bm1s);  // terms_m's power and the accept's
             ts[0] += obj.c1 * (den * p);
             ts[1] += (MODE == 4 ? (double)(obj.c2f * (float)g) : obj.c2 * g) * p;
-            xs[i] = xt;
-            ps[i] = p;
+            stp<kW>(xs + i, (V)xt);
+            stp<kW>(ps + i, (V)p);
             return g * (p / den);
           });
       team_sum<2>(ts, red, tm);
@@ -1333,20 +1350,20 @@ __device__ __forceinline__ void ls_phase(const SolveArgs& A, int img) {
     struct LsIn {
       double x0, g, p0, bkv;
     };
-    row_inv2<BSGP_LS1_PRE, kLs1Jch, kLsComp, COOP, BSGP_LS1_PIPE, 13>(
+    row_inv2<BSGP_LS1_PRE, kLs1Jch, kLsComp, COOP, BSGP_LS1_PIPE, 13, POL>(
         G, Pt, B.spec, lds,
         [&](int r, int j) {
           const int i = r * G.W + j;
           LsIn q;
-          q.x0 = B.xtf[i];
-          q.g = g_raw(g32, B.gns, i);
-          q.p0 = opt_ld(series, B.pw, i, 0.0);
-          q.bkv = opt_ld(bmap, B.bks, i, bks_scalar);
+          q.x0 = ldp<kO8>(B.xtf + i);
+          q.g = g_raw<kO8>(g32, B.gns, i);
+          q.p0 = opt_ld<kO8>(series, B.pw, i, 0.0);
+          q.bkv = opt_ld<kO8>(bmap, B.bks, i, bks_scalar);
           return q;
         },
         [&](int r, int j, double v, const LsIn& q) {
       const int i = r * G.W + j;
-      B.dtf[i] = v;
+      stp<kW>(B.dtf + i, (V)v);
       const double g = gdec(q.g);
       const double x0 = q.x0;
       const double bkv = q.bkv;
@@ -1568,10 +1585,10 @@ __device__ __forceinline__ void ls_phase(const SolveArgs& A, int img) {
           struct Ld {
             double2 x, d, g, b;
           } v;
-          v.x = ld2(xtf, p);
-          v.d = ld2(dtf, p);
-          v.g = g_raw2(g32, gns, p);  // compact: the pair's two f32 in the first f64
-          v.b = opt_ld2(bmap, bks, p, bks_scalar);
+          v.x = ld2<kO8>(xtf, p);
+          v.d = ld2<kO8>(dtf, p);
+          v.g = g_raw2<kO8>(g32, gns, p);  // compact: the pair's two f32 in the first f64
+          v.b = opt_ld2<kO8>(bmap, bks, p, bks_scalar);
           return v;
         },
         [&](int p, const auto& v) {
@@ -1624,22 +1641,22 @@ __device__ __forceinline__ void ls_phase(const SolveArgs& A, int img) {
     double x, d, g, bkv, p0;
   };
   if (!spec_acc) {
-    row_fwd2<kLsAccJch, kLsAccPf, kLsComp, COOP, BSGP_LSACC_PIPE, 16>(
+    row_fwd2<kLsAccJch, kLsAccPf, kLsComp, COOP, BSGP_LSACC_PIPE, 16, POL>(
         G, Pt, G.H, G.W, G.sld, B.spec, lds,
         [&](int r, int j) {
           const int i = r * G.W + j;
           AcIn q;
-          q.x = B.xtf[i];
-          q.d = B.dtf[i];
-          q.g = g_raw(g32, B.gns, i);
-          q.bkv = opt_ld(bmap, B.bks, i, bks_scalar);
-          q.p0 = opt_ld(pw_series, B.pw, i, 0.0);
+          q.x = ldp<kO8>(B.xtf + i);
+          q.d = ldp<kO8>(B.dtf + i);
+          q.g = g_raw<kO8>(g32, B.gns, i);
+          q.bkv = opt_ld<kO8>(bmap, B.bks, i, bks_scalar);
+          q.p0 = opt_ld<kO8>(pw_series, B.pw, i, 0.0);
           return q;
         },
         [&](int r, int j, const AcIn& q) {
           const int i = r * G.W + j;
           const double xt = q.x + lam_acc * q.d;
-          B.xtf[i] = xt;
+          stp<kW>(B.xtf + i, (V)xt);
           const double den = xt + q.bkv;
           const double g = gdec(q.g);
           if (P.variant != BSGP_VARIANT_BETA) return g / den;  // KL: w = gn/den
@@ -1654,7 +1671,7 @@ __device__ __forceinline__ void ls_phase(const SolveArgs& A, int img) {
           } else {
             p = fpow(den, bm1);
           }
-          B.pw[i] = p;
+          stp<kW>(B.pw + i, (V)p);
           return g * (p / den);
         });
   }
@@ -1662,7 +1679,7 @@ __device__ __forceinline__ void ls_phase(const SolveArgs& A, int img) {
   if (A.fuse_col & 2) {  // AT's column pass follows here
     PH_T(tc0);
     team_sync(tm);
-    col_conv<COOP>(G, Pt, B.spec, tf_of(G, img, 1), lds);
+    col_conv<COOP, POL>(G, Pt, B.spec, tf_of(G, img, 1), lds);
     PH_ADD(3, tc0);
   }
   PH_ADD(7, tk0);
@@ -1698,8 +1715,9 @@ __global__ void __launch_bounds__(kBlock) BSGP_LS_ATTR k_ls(SolveArgs A) {
 // sgp.py:337-414 (= 785-879): g_new = g1(den) - AT(w), x += lam*d, the
 // Barzilai-Borwein step lengths with the tau alternation, the stop rules,
 // and the outputs once the image stops (sgp.py:424-438).
-template <bool COOP, class V>
+template <bool COOP, class V, unsigned POL = 0>
 __device__ __forceinline__ void bb_phase(const SolveArgs& A, int img) {
+  constexpr bool kO16 = (POL & kNtO16) != 0, kO8 = (POL & kNtO8) != 0, kW = (POL & kNtW) != 0;
   BSGP_LDS_VIEWS(A);
   ImgState& st = A.st[img];
   PH_T(tk0);
@@ -1728,14 +1746,14 @@ __device__ __forceinline__ void bb_phase(const SolveArgs& A, int img) {
   struct BbIn {
     double p, x, g;
   };
-  row_inv2<BSGP_BB_PRE, kBbJch, kBbComp, COOP, BSGP_BB_PIPE, 19>(
+  row_inv2<BSGP_BB_PRE, kBbJch, kBbComp, COOP, BSGP_BB_PIPE, 19, POL>(
       G, Pt, B.spec, lds,
       [&](int r, int j) {
         const int i = r * G.W + j;
         BbIn q;
-        q.p = opt_ld(beta_obj, B.pw, i, 1.0);
-        q.x = B.xa[i];
-        q.g = B.ga[i];
+        q.p = opt_ld<kO8>(beta_obj, B.pw, i, 1.0);
+        q.x = ldp<kO8>(B.xa + i);
+        q.g = ldp<kO8>(B.ga + i);
         return q;
       },
       [&](int r, int j, double at, const BbIn& q) {
@@ -1756,12 +1774,13 @@ __device__ __forceinline__ void bb_phase(const SolveArgs& A, int img) {
     bb[3] += yk2 * yk2;
     bb[4] += sk * sk;
     bb[5] += xn * xn;
-    B.xb[i] = xn;
-    B.gb[i] = gnew;
+    stp<kW>(B.xb + i, (V)xn);
+    stp<kW>(B.gb + i, (V)gnew);
   },
       [&](int r, int j) {
         const int p = (r * G.W + j) >> 1;
-        const double2 pw = opt_ld2(beta_obj, B.pw, p, 1.0), x = ld2(B.xa, p), g = ld2(B.ga, p);
+        const double2 pw = opt_ld2<kO16>(beta_obj, B.pw, p, 1.0), x = ld2<kO16>(B.xa, p),
+                      g = ld2<kO16>(B.ga, p);
         return Two<BbIn>{BbIn{pw.x, x.x, g.x}, BbIn{pw.y, x.y, g.y}};
       });
   if (row_wide<COOP>(G)) {
@@ -1933,11 +1952,11 @@ template <bool COOP, class V>
 __device__ __attribute__((noinline)) void persist_setup(ArgRef r, int img) {
   setup_phase<COOP, V>(args_of(r), __builtin_amdgcn_readfirstlane(img));
 }
-template <bool COOP, class V>
+template <bool COOP, class V, unsigned POL>
 __device__ __attribute__((noinline)) void persist_dir(ArgRef r, int img) {
-  dir_phase<COOP, V, false>(args_of(r), __builtin_amdgcn_readfirstlane(img));
+  dir_phase<COOP, V, false, POL>(args_of(r), __builtin_amdgcn_readfirstlane(img));
 }
-template <bool COOP>
+template <bool COOP, unsigned POL>
 __device__ __attribute__((noinline)) void persist_col_a(ArgRef r, int img) {
   const SolveArgs& A = args_of(r);
   img = __builtin_amdgcn_readfirstlane(img);
@@ -1948,17 +1967,18 @@ __device__ __attribute__((noinline)) void persist_col_a(ArgRef r, int img) {
   const Bufs<double> Bd = slot_bufs<double>(A, img, 0);  // spec only (same offset for V)
   PH_T(tc0);
   // (a cooperative plan's column pass on its column groups, as k_col)
-  col_conv<COOP>(A.g, make_part(tm, COOP ? A.g.nfc : A.g.nfw, A.g.W), Bd.spec,
-                 tf_of(A.g, img, 0), lds);
+  col_conv<COOP, POL>(A.g, make_part(tm, COOP ? A.g.nfc : A.g.nfw, A.g.W), Bd.spec,
+                      tf_of(A.g, img, 0), lds);
   PH_ADD(3, tc0);
 }
-template <int K, int MODE, bool ADAPT, bool COOP, class V, bool SB = false>
+template <int K, int MODE, bool ADAPT, bool COOP, class V, bool SB, unsigned POL>
 __device__ __attribute__((noinline)) void persist_ls(ArgRef r, int img) {
-  ls_phase<K, MODE, ADAPT, COOP, V, SB, true>(args_of(r), __builtin_amdgcn_readfirstlane(img));
+  ls_phase<K, MODE, ADAPT, COOP, V, SB, true, POL>(args_of(r),
+                                                   __builtin_amdgcn_readfirstlane(img));
 }
-template <bool COOP, class V>
+template <bool COOP, class V, unsigned POL>
 __device__ __attribute__((noinline)) void persist_bb(ArgRef r, int img) {
-  bb_phase<COOP, V>(args_of(r), __builtin_amdgcn_readfirstlane(img));
+  bb_phase<COOP, V, POL>(args_of(r), __builtin_amdgcn_readfirstlane(img));
 }
 
 // Slot order (fixed-length solves, stop rules 0/1): task t = (k - 1) * nimg + i
@@ -1980,6 +2000,10 @@ __global__ void __launch_bounds__(kBlock) BSGP_PERSIST_ATTR k_persist(SolveArgs 
   (void)red;
   __shared__ int s_img;
   __shared__ unsigned s_k;
+  // the unit's stream policy; the adaptive-beta builds stay plain: they are the
+  // star stamps', 31x31 images whose whole slot lives in the L2, where every
+  // non-temporal class lost (stamps31 -1.5 % with the float64 unit's mask)
+  constexpr unsigned kPol = ADAPT ? 0u : (unsigned)(BSGP_STREAM_NT);
   const int tid = threadIdx.x;
   const Geo& G = A.g;
   load_tw_lds(G);
@@ -2075,12 +2099,12 @@ __global__ void __launch_bounds__(kBlock) BSGP_PERSIST_ATTR k_persist(SolveArgs 
     if (fs && k == 1) {
       persist_setup<COOP, V>(ar, img);  // the image's first task: its setup
     } else {
-      persist_dir<COOP, V>(ar, img);
+      persist_dir<COOP, V, kPol>(ar, img);
       __syncthreads();  // rows of d and the direction scalars complete
-      persist_col_a<COOP>(ar, img);
-      persist_ls<K, MODE, ADAPT, COOP, V, SB>(ar, img);
+      persist_col_a<COOP, kPol>(ar, img);
+      persist_ls<K, MODE, ADAPT, COOP, V, SB, kPol>(ar, img);
       __syncthreads();  // the accepted step and AT's columns complete
-      persist_bb<COOP, V>(ar, img);
+      persist_bb<COOP, V, kPol>(ar, img);
     }
     // hand the image on: every wave's stores drained, then lane 0 releases at
     // agent scope and publishes (sc1 store): ring append, or done[img]

@@ -15,6 +15,15 @@
 #ifndef BSGP_LS1_K2
 #define BSGP_LS1_K2 1
 #endif
+// stream policy of this build's phases (bsgp_device.hpp, "cache policy"):
+// O16 | W | SC = the wide operand loads, the operand stores and the column
+// pass's spectrum accesses are non-temporal (C3 +2.3 % against plain, same
+// box; DESIGN §8 has every mask).  The row-side spectrum (SR) must stay plain:
+// its 32-byte pieces of a line are merged across waves in the caches, -36 %
+// with nt.  The other persistent units keep the header's 0.
+#ifndef BSGP_STREAM_NT
+#define BSGP_STREAM_NT 21
+#endif
 #include "bsgp_kernels.hpp"
 
 namespace bsgp {
