@@ -155,6 +155,8 @@ def lib():
             L.bsgp_fits_to_f64.argtypes = [vp, i64, i32, dbl, dbl, vp, vp]
             L.bsgp_psf_stamps.argtypes = [ctypes.POINTER(PsfModel), vp, i32, i32, i32, vp, vp]
             L.bsgp_plan_set_psfs.argtypes = [vp, vp, i32, vp]
+            L.bsgp_plan_set_static_geo.argtypes = [vp, i32]
+            L.bsgp_plan_static_geo.argtypes = [vp, vp]
             L.bsgp_state_layout.argtypes = [i32, i32, i32, i32, i32, vp]
             L.bsgp_state_bytes.argtypes = [vp, i32, i32, ctypes.POINTER(i64)]
             L.bsgp_state_save.argtypes = [vp, i32, vp, i64, vp]
@@ -174,7 +176,8 @@ def lib():
                          "bsgp_psf_stamps", "bsgp_plan_set_psfs", "bsgp_state_layout",
                          "bsgp_state_bytes", "bsgp_state_save", "bsgp_solve_resume",
                          "bsgp_background2d", "bsgp_convolve2d", "bsgp_detect_sources",
-                         "bsgp_segment_catalog"]:
+                         "bsgp_segment_catalog", "bsgp_plan_set_static_geo",
+                         "bsgp_plan_static_geo"]:
                 getattr(L, name).restype = ctypes.c_int
             if L.bsgp_abi_version() != ABI_VERSION:
                 raise BsgpError(-3, f"{LIB_PATH} has ABI {L.bsgp_abi_version()}, this binding "
@@ -189,7 +192,8 @@ EXPORTED = ["bsgp_plan_create", "bsgp_plan_create_checked", "bsgp_plan_destroy",
             "bsgp_last_error", "bsgp_abi_version", "bsgp_extract_tiles", "bsgp_coadd_tiles",
             "bsgp_fits_to_f64", "bsgp_psf_stamps", "bsgp_plan_set_psfs", "bsgp_state_layout",
             "bsgp_state_bytes", "bsgp_state_save", "bsgp_solve_resume", "bsgp_background2d",
-            "bsgp_convolve2d", "bsgp_detect_sources", "bsgp_segment_catalog"]
+            "bsgp_convolve2d", "bsgp_detect_sources", "bsgp_segment_catalog",
+            "bsgp_plan_set_static_geo", "bsgp_plan_static_geo"]
 
 
 def check(rc):
@@ -264,6 +268,19 @@ class Plan:
         check(lib().bsgp_plan_set_psfs(self.h, _ptr(psfs), psfs.shape[0], current_stream()))
         self.n_psf = psfs.shape[0]
         return self
+
+    def set_static_geo(self, mode):
+        """The compile-time-geometry path of the persistent solver for the NEXT
+        solve / resume on this plan only: None = the default (BSGP_STATIC_GEO,
+        else on), 0 / 1 (bsgp_plan_set_static_geo)."""
+        check(lib().bsgp_plan_set_static_geo(self.h, -1 if mode is None else int(bool(mode))))
+        return self
+
+    def static_geo_used(self):
+        """Whether the plan's last solve took that path (bsgp_plan_static_geo)."""
+        used = ctypes.c_int32()
+        check(lib().bsgp_plan_static_geo(self.h, ctypes.byref(used)))
+        return bool(used.value)
 
     def apply(self, x, transpose=False):
         """A(x) / AT(x) on a [B,H,W] (or [H,W]) float64 CUDA tensor."""

@@ -211,6 +211,20 @@ struct bsgp_plan_s {
   bsgp_params last_prm{};
   bsgp_outputs last_out{};
   int last_B = 0, last_T = 0, last_beta0 = 0;
+  // compile-time-geometry path of the persistent solver (bsgp_plan_set_static_geo):
+  // the next solve's choice (-1: BSGP_STATIC_GEO, default 1), and whether the
+  // last solve took the path
+  int static_geo_next = -1;
+  int last_static_geo = 0;
+};
+
+// A solve entry point that can fail before solve_impl: the choice of
+// bsgp_plan_set_static_geo belongs to this call whatever becomes of it, and
+// until a solve runs the plan reports no static path.
+struct StaticGeoCall {
+  bsgp_plan p;
+  explicit StaticGeoCall(bsgp_plan q) : p(q) { p->last_static_geo = 0; }
+  ~StaticGeoCall() { p->static_geo_next = -1; }
 };
 
 // Capacity of one thread's projection list: the pixels it streams in one pass
@@ -752,6 +766,19 @@ int bsgp_plan_set_psfs(bsgp_plan p, const double* psfs, int32_t n, void* stream)
   return BSGP_OK;
 }
 
+int bsgp_plan_set_static_geo(bsgp_plan p, int32_t mode) {
+  if (!p) return fail(BSGP_ERR_ARG, "plan is NULL");
+  if (mode < -1 || mode > 1) return fail(BSGP_ERR_ARG, "static_geo must be -1, 0 or 1");
+  p->static_geo_next = mode;
+  return BSGP_OK;
+}
+
+int bsgp_plan_static_geo(bsgp_plan p, int32_t* used) {
+  if (!p || !used) return fail(BSGP_ERR_ARG, "plan or used is NULL");
+  *used = p->last_static_geo;
+  return BSGP_OK;
+}
+
 int bsgp_plan_info(bsgp_plan p, int32_t* P, int32_t* Q, int64_t* slot_bytes,
                    int32_t* fft_waves) {
   if (!p) return fail(BSGP_ERR_ARG, "plan is NULL");
@@ -811,6 +838,7 @@ int bsgp_solve_profiled(bsgp_plan p, int32_t B, const bsgp_params* prm, const bs
   if (!kernel_ms || !launches) return fail(BSGP_ERR_ARG, "kernel_ms / launches missing");
   if (!prm) return fail(BSGP_ERR_ARG, "params is NULL");
   if (!p) return fail(BSGP_ERR_ARG, "plan is NULL");
+  StaticGeoCall sgc(p);
   DEVICE_SCOPE(p->device);
   SolveProf prof;
   prof.kernel_ms = kernel_ms;
@@ -834,6 +862,11 @@ static int solve_impl(bsgp_plan p, int32_t B, const bsgp_params* prm, const bsgp
                       const bsgp_outputs* out, void* stream, SolveProf* prof,
                       const ResumeCtx* rs) {
   if (!p) return fail(BSGP_ERR_ARG, "plan is NULL");
+  // bsgp_plan_set_static_geo's choice is this call's alone, also when the call
+  // fails below before anything runs (then no path was taken)
+  const int static_geo_choice = p->static_geo_next;
+  p->static_geo_next = -1;
+  p->last_static_geo = 0;
   int rc = check_params(prm);
   if (rc) return rc;
   if (B < 1) return fail(BSGP_ERR_ARG, "B must be >= 1");
@@ -890,6 +923,7 @@ static int solve_impl(bsgp_plan p, int32_t B, const bsgp_params* prm, const bsgp
   // one-workgroup images run AT's column pass at the end of k_ls (bit 1);
   // teams launch k_col for it
   a.fuse_col = T == 1 ? 2 : 0;
+  a.static_geo = 0;
   a.tpart = T > 1 ? p->tpart : nullptr;
   a.tctr = p->tctr;
   a.tfail = reinterpret_cast<int*>(p->tctr + (size_t)B * kTeamWords);
@@ -941,6 +975,16 @@ static int solve_impl(bsgp_plan p, int32_t B, const bsgp_params* prm, const bsgp
   const bool persist =
       prm->persistent && T == 1 && !track && (!rs || ring_rule || rs->uniform);
   if (persist) S = 1;
+  // the flagship plan's compile-time-geometry phases (k_persist): this solve's
+  // choice (bsgp_plan_set_static_geo, else BSGP_STATIC_GEO, default on), taken
+  // only when the kernel launched carries them and every plan value they fold
+  // equals the plan's own
+  {
+    const int want = static_geo_choice >= 0 ? static_geo_choice
+                                            : (int)env_knob("BSGP_STATIC_GEO", 1, 0, 1);
+    a.static_geo = (want && persist && persist_static_geo(a, K)) ? 1 : 0;
+    p->last_static_geo = a.static_geo;
+  }
   // fixed-length persistent solves run every image's setup as the first task
   // of its chain inside k_persist: the setups of the last images overlap the
   // first iterations of the others, with no k_setup launch and no boundary
@@ -1253,6 +1297,7 @@ int bsgp_solve_resume(bsgp_plan p, int32_t B, const bsgp_params* prm, const void
                       int32_t n_state, int64_t bytes_per_image, const int32_t* index,
                       const bsgp_outputs* out, void* stream) {
   if (!p) return fail(BSGP_ERR_ARG, "plan is NULL");
+  StaticGeoCall sgc(p);
   int rc = check_params(prm);
   if (rc) return rc;
   if (!state_dev || n_state < 1) return fail(BSGP_ERR_ARG, "state_dev missing");

@@ -96,8 +96,63 @@ struct Geo {
 };
 
 // Transfer function image `img` uses (bsgp_plan_set_psfs gives every image its own).
-__device__ __forceinline__ const cd* tf_of(const Geo& G, int img, int transpose) {
+template <class GT = Geo>
+__device__ __forceinline__ const cd* tf_of(const GT& G, int img, int transpose) {
   return (transpose ? G.tfAT : G.tfA) + (size_t)img * G.tf_stride;
+}
+
+// Compile-time geometry (the geometry policy of the per-wave row and column
+// helpers, which take the geometry as a template type: the runtime Geo, or
+// this).  The same member names as Geo, as constants derived by the formulas
+// of bsgp_plan_create for a per-wave plan whose transforms and twiddle tables
+// fit the LDS at four workgroups' budget; only the TF pointers stay runtime
+// values.  The host selects it for a solve only when the plan's own values
+// equal these (static_geo_plan, bsgp_kernels.hpp), so a phase instantiated on
+// it addresses exactly what the runtime path addresses, with the index
+// arithmetic, the bounds tests and the transform dispatch folded.
+// A transform length known at compile time, its twiddles at byte OFF of the
+// dynamic LDS (fft_any below).
+template <int N, int OFF>
+struct SPlan {
+  static constexpr int n = N;
+  static constexpr int lds_tw = OFF;
+};
+template <int H_, int W_, int P_, int Q_>
+struct SGeo {
+  static constexpr int H = H_, W = W_, P = P_, Q = Q_;
+  static constexpr int Qh = Q_ / 2 + 1;
+  static constexpr int nfw = kWaves, nfc = kWaves, coop = 0;
+  static constexpr int maxlen = P_ > Q_ ? P_ : Q_;
+  static constexpr int lpad = (maxlen + 1 > 2 * Qh ? maxlen + 1 : 2 * Qh) | 1;
+  static constexpr int sld = H_ + (H_ & 1);
+  static constexpr int tw2 = 0, twmix = -1;
+  static constexpr int lds_fft_bytes = nfw * 2 * lpad * (int)sizeof(cd);
+  // after the transform buffers and the reduction scratch; one table when P == Q
+  static constexpr int lds_tw_p =
+      lds_fft_bytes + kWaves * kMaxRed * (int)sizeof(double) + kSharedBytes;
+  static constexpr int lds_tw_q = P_ == Q_ ? lds_tw_p : lds_tw_p + P_ * (int)sizeof(cd);
+  static constexpr int lds_bytes = lds_tw_q + Q_ * (int)sizeof(cd);
+  static constexpr SPlan<P_, lds_tw_p> fp{};
+  static constexpr SPlan<Q_, lds_tw_q> fq{};
+  const cd* tfA;
+  const cd* tfAT;
+  size_t tf_stride;
+};
+template <class GT>
+struct IsStaticGeo : std::false_type {};
+template <int H_, int W_, int P_, int Q_>
+struct IsStaticGeo<SGeo<H_, W_, P_, Q_>> : std::true_type {};
+// the flagship plan: 256 x 256 images, 25 x 25 PSF, linear mode
+using SGeo256 = SGeo<256, 256, 270, 270>;
+static_assert(SGeo256::Qh == 136 && SGeo256::sld == 256 && SGeo256::lpad == 273, "geometry");
+
+// The transform of a static plan: one compile-time length, its twiddles in LDS.
+template <bool COMP = true, int N, int OFF, class Sync>
+__device__ __forceinline__ cd* fft_any(cd* a, cd* b, const SPlan<N, OFF>&, bool inv, int lane,
+                                       int nlanes, Sync sync) {
+  extern __shared__ __attribute__((aligned(16))) char bsgp_dyn_lds[];
+  const cd* t = reinterpret_cast<const cd*>(bsgp_dyn_lds + OFF);
+  return fft_run_static<N, COMP>(a, b, t, inv, lane, nlanes, sync);
 }
 
 // Copy the twiddle tables of the static-length transforms into their LDS slot
@@ -1024,8 +1079,8 @@ __device__ __forceinline__ void half_swap(T& a, T& b) {
 
 // Whether the per-wave row passes of this plan load wide where they have a
 // wide loader (the condition row_fwd2 / row_inv2 test; wave-uniform)
-template <bool COOP>
-__device__ __forceinline__ bool row_wide(const Geo& G) {
+template <bool COOP, class GT = Geo>
+__device__ __forceinline__ bool row_wide(const GT& G) {
   return !COOP && (G.W & 1) == 0;
 }
 
@@ -1587,6 +1642,15 @@ __device__ __forceinline__ void coop_col_conv(const Geo& G, const Part& D, cd* s
     coop_col_conv_g(G, D, spec, tf, lds);
 }
 
+// Whether row pair r has its second row (r even, nrows == G.H in every pass):
+// always, on a static geometry of even height.
+template <class GT>
+__device__ __forceinline__ bool row_two(const GT&, int r, int nrows) {
+  if constexpr (IsStaticGeo<GT>::value) {
+    if constexpr ((GT::H & 1) == 0) return true;
+  }
+  return (r + 1) < nrows;
+}
 // row_fwd2: for every pair of image rows (r, r+1) one wave FFTs z = a + i b
 // (a, b real rows of length ncols zero-padded to Q) and stores the two half
 // spectra into column-major spec with leading dimension ld (>= nrows).
@@ -1601,8 +1665,8 @@ __device__ __forceinline__ void coop_col_conv(const Geo& G, const Part& D, cd* s
 // length take it, odd lengths and cooperative plans keep ld.
 template <int JCH = kJCH, bool PF = false, bool COMP = true, bool COOP = false,
           bool PIPE = false, int PHS = -1, unsigned POL = 0, class LD, class MK,
-          class LD2 = NoWide>
-__device__ __forceinline__ void row_fwd2(const Geo& G, const Part& D, int nrows, int ncols,
+          class LD2 = NoWide, class GT = Geo>
+__device__ __forceinline__ void row_fwd2(const GT& G, const Part& D, int nrows, int ncols,
                                          int ldim, cd* spec, cd* lds, LD&& ld, MK&& mk,
                                          LD2&& ld2 = LD2{}) {
   if constexpr (COOP) {
@@ -1629,10 +1693,10 @@ __device__ __forceinline__ void row_fwd2(const Geo& G, const Part& D, int nrows,
     cd* b = a + G.lpad;
     int r = 2 * (D.gw0 + w);
     V v0[JCH], v1[JCH];
-    if (PF && r < nrows) load(r, (r + 1) < nrows, 0, v0, v1);
+    if (PF && r < nrows) load(r, row_two(G, r, nrows), 0, v0, v1);
     PH_SUB_T(tph);
     for (; r < nrows; r += 2 * D.gws) {
-      const bool two = (r + 1) < nrows;
+      const bool two = row_two(G, r, nrows);
       auto put = [&](int j0, const V (&w0)[JCH], const V (&w1)[JCH]) __attribute__((always_inline)) {
 #pragma unroll
         for (int u = 0; u < JCH; ++u) {
@@ -1673,7 +1737,7 @@ __device__ __forceinline__ void row_fwd2(const Geo& G, const Part& D, int nrows,
         }
       }
       const int rn = r + 2 * D.gws;
-      if (PF && rn < nrows) load(rn, (rn + 1) < nrows, 0, v0, v1);
+      if (PF && rn < nrows) load(rn, row_two(G, rn, nrows), 0, v0, v1);
       wave_sync();
       PH_SUB(PHS, tph);
       cd* Z = fft_any<COMP>(a, b, G.fq, false, lane, 64, WaveSync());
@@ -1708,8 +1772,8 @@ __device__ __forceinline__ void row_fwd(const Geo& G, const Part& D, int nrows, 
 
 // Rebuild the full-length spectrum of row pair (r, r+1) into `a`: each
 // stored column k < Qh is loaded once and yields Z_k and Z_{Q-k}.
-template <unsigned POL = 0>
-__device__ __forceinline__ void gather_pair(const Geo& G, const cd* spec, int ld, int r, bool two,
+template <unsigned POL = 0, class GT = Geo>
+__device__ __forceinline__ void gather_pair(const GT& G, const cd* spec, int ld, int r, bool two,
                                             cd* a, int lane) {
   constexpr bool NT = (POL & kNtSR) != 0;
   for (int k0 = lane; k0 < G.Qh; k0 += 64 * kGCH) {
@@ -1741,8 +1805,8 @@ __device__ __forceinline__ void gather_pair(const Geo& G, const cd* spec, int ld
 // per row touched 64 and asked for every line twice.  Needs lpad >= 2*Qh.
 typedef __attribute__((address_space(3))) void lds_void_t;
 typedef __attribute__((address_space(1))) void gbl_void_t;
-template <unsigned POL = 0>
-__device__ __forceinline__ void stage_pair(const Geo& G, const cd* spec, int ld, int r, bool two,
+template <unsigned POL = 0, class GT = Geo>
+__device__ __forceinline__ void stage_pair(const GT& G, const cd* spec, int ld, int r, bool two,
                                            cd* F, int lane) {
   constexpr int kAux = (POL & kNtSR) ? 2 : 0;  // aux bit 1: nt
   for (int k0 = 0; k0 < G.Qh; k0 += 32) {
@@ -1754,7 +1818,8 @@ __device__ __forceinline__ void stage_pair(const Geo& G, const cd* spec, int ld,
   }
 }
 // Full-length spectrum of the staged pair into `a` (as gather_pair).
-__device__ __forceinline__ void unpack_pair(const Geo& G, const cd* F, bool two, cd* a, int lane) {
+template <class GT = Geo>
+__device__ __forceinline__ void unpack_pair(const GT& G, const cd* F, bool two, cd* a, int lane) {
   for (int k = lane; k < G.Qh; k += 64) {
     const cd A = F[2 * k];
     const cd B = two ? F[2 * k + 1] : cmk(0.0, 0.0);
@@ -1775,8 +1840,8 @@ __device__ __forceinline__ void unpack_pair(const Geo& G, const cd* F, bool two,
 // ld2: as row_fwd2.
 template <bool PRE, int JCH = kJCH, bool COMP = true, bool COOP = false,
           bool PIPE = false, int PHS = -1, unsigned POL = 0, class LD, class USE,
-          class LD2 = NoWide>
-__device__ __forceinline__ void row_inv2(const Geo& G, const Part& D, const cd* spec, cd* lds,
+          class LD2 = NoWide, class GT = Geo>
+__device__ __forceinline__ void row_inv2(const GT& G, const Part& D, const cd* spec, cd* lds,
                                          LD&& ld, USE&& use, LD2&& ld2 = LD2{}) {
   if constexpr (COOP) {
     coop_row_inv(G, D, spec, lds, ld, use);
@@ -1799,9 +1864,9 @@ __device__ __forceinline__ void row_inv2(const Geo& G, const Part& D, const cd* 
     cd* other = in + G.lpad;
     int r = 2 * (D.gw0 + w);
     PH_SUB_T(tph);
-    if (r < G.H) gather_pair<POL>(G, spec, G.sld, r, (r + 1) < G.H, in, lane);
+    if (r < G.H) gather_pair<POL>(G, spec, G.sld, r, row_two(G, r, G.H), in, lane);
     for (; r < G.H; r += 2 * D.gws) {
-      const bool two = (r + 1) < G.H;
+      const bool two = row_two(G, r, G.H);
       V v0[JCH], v1[JCH];
       if (PRE) load(r, two, 0, v0, v1);
       wave_sync();
@@ -1810,7 +1875,7 @@ __device__ __forceinline__ void row_inv2(const Geo& G, const Part& D, const cd* 
       PH_SUB(PHS + 1, tph);
       cd* F = (Z == in) ? other : in;
       const int rn = r + 2 * D.gws;
-      const bool next = rn < G.H, two_n = (rn + 1) < G.H;
+      const bool next = rn < G.H, two_n = row_two(G, rn, G.H);
       if (next) stage_pair<POL>(G, spec, G.sld, rn, two_n, F, lane);
       auto eat = [&](int j0, const V (&w0)[JCH], const V (&w1)[JCH]) __attribute__((always_inline)) {
 #pragma unroll
@@ -1926,8 +1991,8 @@ __device__ __forceinline__ void row_inv_fwd(const Geo& G, const Part& D, cd* spe
 // r2c_split), so sums and spectra have the bits of the two separate passes.
 // Both transform buffers are busy until the forward FFT: the next pair's
 // spectrum is gathered through registers, not staged ahead.
-template <int JCH = kJCH, bool COMP = true, unsigned POL = 0, class LD, class CP>
-__device__ __forceinline__ void row_inv_fwd2(const Geo& G, const Part& D, cd* spec, cd* lds,
+template <int JCH = kJCH, bool COMP = true, unsigned POL = 0, class LD, class CP, class GT = Geo>
+__device__ __forceinline__ void row_inv_fwd2(const GT& G, const Part& D, cd* spec, cd* lds,
                                              LD&& ld, CP&& cp) {
   using V = decltype(ld(0, 0));
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -1936,7 +2001,7 @@ __device__ __forceinline__ void row_inv_fwd2(const Geo& G, const Part& D, cd* sp
     cd* a = lds + w * 2 * G.lpad;
     cd* b = a + G.lpad;
     for (int r = 2 * (D.gw0 + w); r < G.H; r += 2 * D.gws) {
-      const bool two = (r + 1) < G.H;
+      const bool two = row_two(G, r, G.H);
       gather_pair<POL>(G, spec, G.sld, r, two, a, lane);
       V v0[JCH], v1[JCH];
       load_rows<JCH>(ld, r, two, 0, lane, G.W, v0, v1);
@@ -1979,8 +2044,8 @@ __device__ __forceinline__ void row_inv_fwd2(const Geo& G, const Part& D, cd* sp
 // k_col at 111 VGPRs (4 waves/SIMD) and runs 8 % faster than batching its
 // loads with the column's.
 // POL & kNtSC: the column's loads and stores are non-temporal; the TF's never.
-template <bool COOP = false, unsigned POL = 0>
-__device__ __forceinline__ void col_conv(const Geo& G, const Part& D, cd* spec, const cd* tf,
+template <bool COOP = false, unsigned POL = 0, class GT = Geo>
+__device__ __forceinline__ void col_conv(const GT& G, const Part& D, cd* spec, const cd* tf,
                                          cd* lds) {
   constexpr bool NT = (POL & kNtSC) != 0;
   if constexpr (COOP) {

@@ -74,6 +74,9 @@ struct SolveArgs {
   int T;
   int Tc;               // workgroups per image of k_col (no reductions there: not a team)
   int fuse_col;         // bit 1: AT's column pass runs at the end of k_ls (T == 1: 2, teams: 0)
+  int static_geo;       // persistent solver: the plan is SGeo256's and the kernel carries the
+                        // compile-time-geometry phases, which run (persist_static_geo; the
+                        // word fills the padding before tpart: no offset moves)
   double* tpart;        // [B][kPartBufs][T][kMaxRed] reduction partials
   unsigned int* tctr;   // [B][kTeamWords] barrier words, then the timeout word; zeroed per solve
   int* tfail;           // set by a timed-out barrier spin
@@ -201,6 +204,9 @@ hipError_t phase_prof(unsigned long long* out, int n, int reset);
 hipError_t launch_persist(const SolveArgs& a, int K, size_t lds, hipStream_t s, unsigned* queue,
                           unsigned* done, int grid);
 hipError_t persist_resident_per_cu(const SolveArgs& a, int K, size_t lds, int* per_cu);
+// whether the persistent kernel this solve launches has static-geometry phases
+// for the plan's geometry (SolveArgs::static_geo may then be set)
+bool persist_static_geo(const SolveArgs& a, int K);
 hipError_t persist_phase_prof(unsigned long long* out, int n, int reset);
 void persist_kernels_all(std::vector<const void*>& f);
 

@@ -66,6 +66,14 @@ constexpr int kLs1Jch = 1;
 #ifndef BSGP_STREAM_NT
 #define BSGP_STREAM_NT 0
 #endif
+// Compile-time geometry of the flagship plan (SGeo256, bsgp_device.hpp) in the
+// persistent solver: the unit's eligible kernels (K == 2, general beta, fixed
+// beta, float64 storage, per-wave) carry a second set of phase functions
+// instantiated on it, taken when SolveArgs::static_geo says the plan matches.
+// Only bsgp_persist.hip turns it on; every other unit compiles as without it.
+#ifndef BSGP_STATIC_GEO
+#define BSGP_STATIC_GEO 0
+#endif
 // closed-form line-search trials are evaluated kLsLanes at a time, one per
 // lane (ls_phase)
 constexpr int kLsLanes = 32;
@@ -334,6 +342,42 @@ __device__ __forceinline__ void team_end(ImgState& st, const Team& t) {
     st.bar_base = (int)(t.base + (unsigned int)t.nb);
 }
 __device__ __forceinline__ bool leader(const Team& t) { return t.m == 0 && threadIdx.x == 0; }
+
+// The geometry a phase runs on: the plan's own (runtime values), or a static
+// one carrying only the plan's TF pointers.
+template <class GT>
+__device__ __forceinline__ decltype(auto) geo_of(const SolveArgs& A) {
+  if constexpr (IsStaticGeo<GT>::value) {
+    return GT{A.g.tfA, A.g.tfAT, A.g.tf_stride};
+  } else {
+    return (A.g);
+  }
+}
+// Its team: a static geometry is a one-workgroup image's (no team state read,
+// every team branch of the reductions folds).
+template <class GT>
+__device__ __forceinline__ Team team_of(const SolveArgs& A, int img, const ImgState& st) {
+  if constexpr (IsStaticGeo<GT>::value) {
+    Team t{};
+    t.T = 1;
+    t.G = 1;
+    return t;
+  } else {
+    return make_team(A, img, st);
+  }
+}
+template <class GT>
+__device__ __forceinline__ size_t lds_fft_bytes_of(const SolveArgs& A) {
+  if constexpr (IsStaticGeo<GT>::value) {
+    return (size_t)GT::lds_fft_bytes;
+  } else {
+    return A.lds_fft_bytes;
+  }
+}
+#define BSGP_LDS_VIEWS_G(A, GT)                                                     \
+  extern __shared__ __attribute__((aligned(16))) char smem[];                      \
+  cd* lds = reinterpret_cast<cd*>(smem + geo_of<GT>(A).tw2);                       \
+  double* red = reinterpret_cast<double*>(smem + geo_of<GT>(A).tw2 + lds_fft_bytes_of<GT>(A))
 
 #define BSGP_LDS_VIEWS(A)                                                           \
   extern __shared__ __attribute__((aligned(16))) char smem[];                      \
@@ -954,14 +998,16 @@ __device__ __forceinline__ ProjOut cached_projection(const SolveArgs& A, int img
 // d.g, and the row transforms of d.
 // One image's phase (the kernel below, or the persistent solver's task): the
 // caller has checked st.stop and loaded the twiddles into LDS.
-template <bool COOP, class V, bool LL = true, unsigned POL = 0>
+// GT: the geometry policy (Geo: the plan's runtime values; a static geometry
+// for the persistent solver's compile-time path); the same for every phase.
+template <bool COOP, class V, bool LL = true, unsigned POL = 0, class GT = Geo>
 __device__ __forceinline__ void dir_phase(const SolveArgs& A, int img) {
   constexpr bool kO16 = (POL & kNtO16) != 0, kO8 = (POL & kNtO8) != 0;
-  BSGP_LDS_VIEWS(A);
+  BSGP_LDS_VIEWS_G(A, GT);
   ImgState& st = A.st[img];
   PH_T(tk0);
-  Team tm = make_team(A, img, st);
-  const Geo& G = A.g;
+  Team tm = team_of<GT>(A, img, st);
+  decltype(auto) G = geo_of<GT>(A);
   const Part Pt = make_part(tm, G.nfw, G.W);
   const bsgp_params& P = A.prm;
   const int N = G.H * G.W;
@@ -1087,17 +1133,17 @@ __global__ void __launch_bounds__(kBlock) BSGP_COL_ATTR k_col(SolveArgs A, int t
 // solver's).  It never changes a bit of the result, so builds with and
 // without it stay bitwise equal.
 template <int K, int MODE, bool ADAPT, bool COOP, class V, bool SB = false, bool PRED = false,
-          unsigned POL = 0>
+          unsigned POL = 0, class GT = Geo>
 __device__ __forceinline__ void ls_phase(const SolveArgs& A, int img) {
   constexpr bool kO8 = (POL & kNtO8) != 0, kW = (POL & kNtW) != 0;
   // first pass (fused into the inverse rows of A(d)): one trial lambda = 1,
   // which is where most non-stagnating iterations accept; later passes
   // stream K trial lambdas each.
-  BSGP_LDS_VIEWS(A);
+  BSGP_LDS_VIEWS_G(A, GT);
   ImgState& st = A.st[img];
   PH_T(tk0);
-  Team tm = make_team(A, img, st);
-  const Geo& G = A.g;
+  Team tm = team_of<GT>(A, img, st);
+  decltype(auto) G = geo_of<GT>(A);
   const Part Pt = make_part(tm, G.nfw, G.W);
   const bsgp_params& P = A.prm;
   const int N = G.H * G.W;
@@ -1398,7 +1444,7 @@ __device__ __forceinline__ void ls_phase(const SolveArgs& A, int img) {
     });
     // sums and max|u| in one team barrier (the same bits as team_sum + team_max)
     if (series) {
-      team_sum_max<N1>(t1, umax, red, tm, 25);  // (phase profile slots 25, 26)
+      team_sum_max<N1>(t1, umax, red, tm, 38);  // (phase profile slots 38, 39: its own)
       rho = umax;
     } else {
       team_sum<N1>(t1, red, tm);
@@ -1715,14 +1761,14 @@ __global__ void __launch_bounds__(kBlock) BSGP_LS_ATTR k_ls(SolveArgs A) {
 // sgp.py:337-414 (= 785-879): g_new = g1(den) - AT(w), x += lam*d, the
 // Barzilai-Borwein step lengths with the tau alternation, the stop rules,
 // and the outputs once the image stops (sgp.py:424-438).
-template <bool COOP, class V, unsigned POL = 0>
+template <bool COOP, class V, unsigned POL = 0, class GT = Geo>
 __device__ __forceinline__ void bb_phase(const SolveArgs& A, int img) {
   constexpr bool kO16 = (POL & kNtO16) != 0, kO8 = (POL & kNtO8) != 0, kW = (POL & kNtW) != 0;
-  BSGP_LDS_VIEWS(A);
+  BSGP_LDS_VIEWS_G(A, GT);
   ImgState& st = A.st[img];
   PH_T(tk0);
-  Team tm = make_team(A, img, st);
-  const Geo& G = A.g;
+  Team tm = team_of<GT>(A, img, st);
+  decltype(auto) G = geo_of<GT>(A);
   const Part Pt = make_part(tm, G.nfw, G.W);
   const bsgp_params& P = A.prm;
   const int N = G.H * G.W;
@@ -1952,33 +1998,33 @@ template <bool COOP, class V>
 __device__ __attribute__((noinline)) void persist_setup(ArgRef r, int img) {
   setup_phase<COOP, V>(args_of(r), __builtin_amdgcn_readfirstlane(img));
 }
-template <bool COOP, class V, unsigned POL>
+template <bool COOP, class V, unsigned POL, class GT = Geo>
 __device__ __attribute__((noinline)) void persist_dir(ArgRef r, int img) {
-  dir_phase<COOP, V, false, POL>(args_of(r), __builtin_amdgcn_readfirstlane(img));
+  dir_phase<COOP, V, false, POL, GT>(args_of(r), __builtin_amdgcn_readfirstlane(img));
 }
-template <bool COOP, unsigned POL>
+template <bool COOP, unsigned POL, class GT = Geo>
 __device__ __attribute__((noinline)) void persist_col_a(ArgRef r, int img) {
   const SolveArgs& A = args_of(r);
   img = __builtin_amdgcn_readfirstlane(img);
-  BSGP_LDS_VIEWS(A);
+  BSGP_LDS_VIEWS_G(A, GT);
   (void)red;
   Team tm{};
   tm.T = 1;
   const Bufs<double> Bd = slot_bufs<double>(A, img, 0);  // spec only (same offset for V)
   PH_T(tc0);
+  decltype(auto) G = geo_of<GT>(A);
   // (a cooperative plan's column pass on its column groups, as k_col)
-  col_conv<COOP, POL>(A.g, make_part(tm, COOP ? A.g.nfc : A.g.nfw, A.g.W), Bd.spec,
-                      tf_of(A.g, img, 0), lds);
+  col_conv<COOP, POL>(G, make_part(tm, COOP ? G.nfc : G.nfw, G.W), Bd.spec, tf_of(G, img, 0), lds);
   PH_ADD(3, tc0);
 }
-template <int K, int MODE, bool ADAPT, bool COOP, class V, bool SB, unsigned POL>
+template <int K, int MODE, bool ADAPT, bool COOP, class V, bool SB, unsigned POL, class GT = Geo>
 __device__ __attribute__((noinline)) void persist_ls(ArgRef r, int img) {
-  ls_phase<K, MODE, ADAPT, COOP, V, SB, true, POL>(args_of(r),
-                                                   __builtin_amdgcn_readfirstlane(img));
+  ls_phase<K, MODE, ADAPT, COOP, V, SB, true, POL, GT>(args_of(r),
+                                                       __builtin_amdgcn_readfirstlane(img));
 }
-template <bool COOP, class V, unsigned POL>
+template <bool COOP, class V, unsigned POL, class GT = Geo>
 __device__ __attribute__((noinline)) void persist_bb(ArgRef r, int img) {
-  bb_phase<COOP, V, POL>(args_of(r), __builtin_amdgcn_readfirstlane(img));
+  bb_phase<COOP, V, POL, GT>(args_of(r), __builtin_amdgcn_readfirstlane(img));
 }
 
 // Slot order (fixed-length solves, stop rules 0/1): task t = (k - 1) * nimg + i
@@ -1990,6 +2036,27 @@ __device__ __attribute__((noinline)) void persist_bb(ArgRef r, int img) {
 constexpr unsigned kDoneStop = 0x40000000u;
 __device__ __forceinline__ unsigned ld_sc1_u32(const unsigned* p) {
   return __hip_atomic_load((gu32*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// Kernels that carry the static-geometry phases.  ON: the unit's BSGP_STATIC_GEO,
+// a template argument so that every unit names its own instantiation (one
+// definition per entity, whatever the unit's macro says).
+template <class V, bool ON>
+__host__ __device__ constexpr bool static_geo_kernel(bool coop, int K, int mode, bool adapt) {
+  return ON && !coop && K == 2 && (mode == 3 || mode == 4) && !adapt &&
+         std::is_same<V, double>::value;
+}
+// Whether a plan's geometry is SGeo256's in every value the static phases
+// replace by a constant (the LDS layout of bsgp_plan_create included).
+inline bool static_geo_plan(const SolveArgs& a) {
+  using S = SGeo256;
+  const Geo& g = a.g;
+  return g.H == S::H && g.W == S::W && g.P == S::P && g.Q == S::Q && g.Qh == S::Qh &&
+         g.nfw == S::nfw && g.coop == 0 && g.lpad == S::lpad && g.sld == S::sld &&
+         g.tw2 == S::tw2 && g.twmix == S::twmix && g.fp.n == S::P && g.fq.n == S::Q &&
+         g.fp.lds_tw == S::lds_tw_p && g.fq.lds_tw == S::lds_tw_q &&
+         a.lds_fft_bytes == (size_t)S::lds_fft_bytes && a.T == 1 &&
+         a.storage == BSGP_STORAGE_F64;
 }
 
 template <bool COOP, int K, int MODE, bool ADAPT, class V, bool SB = false>
@@ -2004,6 +2071,7 @@ __global__ void __launch_bounds__(kBlock) BSGP_PERSIST_ATTR k_persist(SolveArgs 
   // star stamps', 31x31 images whose whole slot lives in the L2, where every
   // non-temporal class lost (stamps31 -1.5 % with the float64 unit's mask)
   constexpr unsigned kPol = ADAPT ? 0u : (unsigned)(BSGP_STREAM_NT);
+  constexpr bool kStatic = static_geo_kernel<V, (BSGP_STATIC_GEO != 0)>(COOP, K, MODE, ADAPT);
   const int tid = threadIdx.x;
   const Geo& G = A.g;
   load_tw_lds(G);
@@ -2098,6 +2166,17 @@ __global__ void __launch_bounds__(kBlock) BSGP_PERSIST_ATTR k_persist(SolveArgs 
     const ArgRef ar = kernarg_ref();
     if (fs && k == 1) {
       persist_setup<COOP, V>(ar, img);  // the image's first task: its setup
+    } else if (kStatic && A.static_geo) {
+      // the plan is SGeo256's (the host checked every value): the same phases
+      // on the compile-time geometry, bit for bit the runtime path's results
+      if constexpr (kStatic) {
+        persist_dir<COOP, V, kPol, SGeo256>(ar, img);
+        __syncthreads();
+        persist_col_a<COOP, kPol, SGeo256>(ar, img);
+        persist_ls<K, MODE, ADAPT, COOP, V, SB, kPol, SGeo256>(ar, img);
+        __syncthreads();
+        persist_bb<COOP, V, kPol, SGeo256>(ar, img);
+      }
     } else {
       persist_dir<COOP, V, kPol>(ar, img);
       __syncthreads();  // rows of d and the direction scalars complete

@@ -24,6 +24,11 @@
 #ifndef BSGP_STREAM_NT
 #define BSGP_STREAM_NT 21
 #endif
+// this unit's eligible kernels carry the compile-time-geometry phases of the
+// flagship plan (bsgp_kernels.hpp, BSGP_STATIC_GEO)
+#ifndef BSGP_STATIC_GEO
+#define BSGP_STATIC_GEO 1
+#endif
 #include "bsgp_kernels.hpp"
 
 namespace bsgp {
@@ -40,6 +45,16 @@ hipError_t launch_persist(const SolveArgs& a, int K, size_t lds, hipStream_t s, 
     return bsgp_app_launch_persist(&a, K, lds, s, queue, done, grid);
   if (a.storage == BSGP_STORAGE_F32) return launch_persist_f32(a, K, lds, s, queue, done, grid);
   return launch_persist_t<double>(a, K, lds, s, queue, done, grid);
+}
+
+// The solve takes this unit's float64 kernels (the routing of launch_persist),
+// the kernel it takes has the static phases, and the plan is SGeo256's.
+bool persist_static_geo(const SolveArgs& a, int K) {
+  if (a.g.coop || app_static_plan(a.g, a.storage) || a.storage != BSGP_STORAGE_F64) return false;
+  bool adapt = false;
+  const int mode = ls_mode(a, &adapt);
+  return static_geo_kernel<double, (BSGP_STATIC_GEO != 0)>(false, K >= 2 ? 2 : K, mode, adapt) &&
+         static_geo_plan(a);
 }
 
 // Workgroups of the persistent kernel a solve would launch that one CU holds.

@@ -41,6 +41,7 @@ import errno
 import logging
 import math
 import os
+import threading
 
 import numpy as np
 
@@ -552,7 +553,7 @@ def _solve_batch(variant, gns, psf, bkgs, betaParams=None, flux=None, init_recon
                  lr_exp_param=0.1, schedule_lr=False, ls_spec=None, ls_series=None,
                  streams=None, team=None, proj_cache=None, gn_compact=None,
                  device_out=False, profile=False, storage="f64", gn_f32=None, save=False,
-                 errflag=False, obj=None, persistent=None, return_state=False):
+                 errflag=False, obj=None, persistent=None, return_state=False, static_geo=None):
     torch = _B.torch
     if save or errflag:  # sgp()/sgp_betaDiv() keywords: per-image files / err arrays
         raise ValueError("save / errflag are single-image options: use sgp / sgp_betaDiv")
@@ -617,14 +618,33 @@ def _solve_batch(variant, gns, psf, bkgs, betaParams=None, flux=None, init_recon
         if len(psf) != Bn:
             raise ValueError("one PSF per image: psf must be [B, kh, kw]")
         plan = _B.per_image_plan(H, W, psf, mode, storage=storage)
-        out = plan.solve(gns, bkgs, prm, flux=fl, x0=x0, beta0=b0, profile=profile)
+        out = plan.set_static_geo(static_geo).solve(gns, bkgs, prm, flux=fl, x0=x0, beta0=b0,
+                                                    profile=profile)
+        _last.static_geo = plan.static_geo_used()
     else:
         with _B.lease_plan(H, W, psf, mode, storage=storage) as plan:
-            out = plan.solve(gns, bkgs, prm, flux=fl, x0=x0, beta0=b0, profile=profile)
+            out = plan.set_static_geo(static_geo).solve(gns, bkgs, prm, flux=fl, x0=x0, beta0=b0,
+                                                        profile=profile)
+            _last.static_geo = plan.static_geo_used()
             # the state leaves the plan before the lease ends: the next solve
             # on the plan overwrites its slots
             state = _B.SolverState(plan.save_state(Bn), psf) if return_state else None
     return _finish_batch(out, state, device_out)
+
+
+# what the calling thread's last batched solve / resume reported
+_last = threading.local()
+
+
+def last_static_geo():
+    """Whether the calling thread's last batched solve or resume ran the
+    persistent solver's compile-time-geometry path (``static_geo=None/0/1`` of
+    ``sgp_batch`` / ``sgp_betaDiv_batch``: the default, environment
+    BSGP_STATIC_GEO else on, never, or wherever the plan matches: 256 x 256
+    images on a 270 x 270 grid, linear mode, float64 storage, general fixed
+    beta, one workgroup per image).  Results are bit for bit the same either
+    way."""
+    return bool(getattr(_last, "static_geo", False))
 
 
 def _finish_batch(out, state, device_out):
@@ -659,7 +679,7 @@ def state_params(variant, **kw):
     return _params(code, **d, **kw)
 
 
-_RESUME_TUNING =("streams", "persistent", "proj_cache", "ls_spec", "team")
+_RESUME_TUNING =("streams", "persistent", "proj_cache", "ls_spec", "team", "static_geo")
 
 
 def sgp_resume(state, MAXIT, images=None, device_out=False, return_state=False, **tuning):
@@ -670,8 +690,8 @@ def sgp_resume(state, MAXIT, images=None, device_out=False, return_state=False, 
     unsplit solve returns (``times`` excepted): complete history rows, and
     images that had already stopped unchanged.  ``images`` is an index array:
     a subset or a permutation of the saved images.  ``tuning`` accepts only
-    ``streams``, ``persistent``, ``proj_cache``, ``ls_spec`` (paths that are
-    bit-identical) and ``team``, which must be the saved team size.
+    ``streams``, ``persistent``, ``proj_cache``, ``ls_spec``, ``static_geo`` (paths
+    that are bit-identical) and ``team``, which must be the saved team size.
     ``return_state=True`` adds the new state as ``out["state"]``."""
     torch = _B.torch
     bad = sorted(set(tuning) - set(_RESUME_TUNING))
@@ -683,6 +703,7 @@ def sgp_resume(state, MAXIT, images=None, device_out=False, return_state=False, 
     prm = state.params()
     prm.MAXIT = int(MAXIT)
     prm.team = int(h["T"][0])  # the saved team size, whatever the batch size now
+    static_geo = tuning.pop("static_geo", None)  # (a choice of the solve, not of Params)
     for k, v in tuning.items():
         if v is not None:
             setattr(prm, k, int(v))
@@ -699,7 +720,8 @@ def sgp_resume(state, MAXIT, images=None, device_out=False, return_state=False, 
         index = torch.from_numpy((idx % len(state)).astype(np.int32)).to("cuda")
     storage = int(h["storage"][0])
     with _B.lease_plan(H, W, state.psf, int(h["conv_mode"][0]), storage=storage) as plan:
-        out = plan.resume(dev.records, prm, index=index)
+        out = plan.set_static_geo(static_geo).resume(dev.records, prm, index=index)
+        _last.static_geo = plan.static_geo_used()
         new = (_B.SolverState(plan.save_state(out["iters"].numel()), state.psf)
                if return_state else None)
     return _finish_batch(out, new, device_out)

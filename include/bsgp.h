@@ -446,6 +446,15 @@ int bsgp_segment_catalog(const double* data, const double* conv, const int32_t* 
 
 int bsgp_device_synchronize(void);
 const char* bsgp_last_error(void);
+/* The persistent solver's compile-time-geometry path (256 x 256 images on a
+ * 270 x 270 grid, linear mode, float64 storage, one workgroup per image: the
+ * same results bit for bit, fewer instructions).  bsgp_plan_set_static_geo
+ * chooses for the NEXT solve or resume on the plan only: 1 take it where the
+ * plan matches, 0 never, -1 the default (environment BSGP_STATIC_GEO, else 1).
+ * bsgp_plan_static_geo reports whether the plan's last solve took it. */
+int bsgp_plan_set_static_geo(bsgp_plan plan, int32_t mode);
+int bsgp_plan_static_geo(bsgp_plan plan, int32_t* used);
+
 int32_t bsgp_abi_version(void);
 
 #ifdef __cplusplus

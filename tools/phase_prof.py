@@ -28,10 +28,11 @@ SLOTS = {0: "k_dir projection", 1: "k_dir row pass", 2: "k_dir total", 3: "k_col
          16: "  accept rows: operand batches", 17: "  accept rows: FFT", 18: "  accept rows: stores",
          19: "  bb rows: operand batches", 20: "  bb rows: FFT", 21: "  bb rows: stage/unpack",
          22: "  dir rows: operand batches", 23: "  dir rows: FFT", 24: "  dir rows: stores",
-         25: "  coop rows: spectrum gathers | ls1 red.: own waves", 26: "  coop rows: FFTs | ls1 red.: other members", 27: "  coop rows: operands",
+         25: "  coop rows: spectrum gathers", 26: "  coop rows: FFTs", 27: "  coop rows: operands",
          28: "  coop rows: spectrum stores", 29: "  coop cols: loads", 30: "  coop cols: FFT+TF+store",
          31: "persistent: dequeue + wait for the previous iteration",
-         34: "k_ls replay of skipped sums", 37: "k_ls speculative fused pass"}
+         34: "k_ls replay of skipped sums", 37: "k_ls speculative fused pass",
+         38: "  ls1 team reduction: own waves", 39: "  ls1 team reduction: other members"}
 # line-search prediction counters (events, not cycles): iterations per
 # prediction and the mispredicted ones among them (a replay pass each)
 COUNTS = {32: "predicted accept", 35: "  first trial failed (replay)",
