@@ -167,6 +167,9 @@ def lib():
             L.bsgp_detect_sources.argtypes = [vp, i32, i32, i32, i32, vp, dbl, i32, i32, vp, vp,
                                               vp, vp]
             L.bsgp_segment_catalog.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]
+            L.bsgp_radial_profile.argtypes = [vp, i32, i32, i32, i32, vp, i32, vp, vp, vp]
+            L.bsgp_fit_gauss1d.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]
+            L.bsgp_wasserstein1.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp]
             for name in ["bsgp_plan_create", "bsgp_plan_create_checked", "bsgp_plan_destroy", "bsgp_plan_info",
                          "bsgp_solve_device", "bsgp_solve_host", "bsgp_solve_profiled",
                          "bsgp_apply_operator",
@@ -177,7 +180,8 @@ def lib():
                          "bsgp_state_bytes", "bsgp_state_save", "bsgp_solve_resume",
                          "bsgp_background2d", "bsgp_convolve2d", "bsgp_detect_sources",
                          "bsgp_segment_catalog", "bsgp_plan_set_static_geo",
-                         "bsgp_plan_static_geo"]:
+                         "bsgp_plan_static_geo", "bsgp_radial_profile", "bsgp_fit_gauss1d",
+                         "bsgp_wasserstein1"]:
                 getattr(L, name).restype = ctypes.c_int
             if L.bsgp_abi_version() != ABI_VERSION:
                 raise BsgpError(-3, f"{LIB_PATH} has ABI {L.bsgp_abi_version()}, this binding "
@@ -193,7 +197,8 @@ EXPORTED = ["bsgp_plan_create", "bsgp_plan_create_checked", "bsgp_plan_destroy",
             "bsgp_fits_to_f64", "bsgp_psf_stamps", "bsgp_plan_set_psfs", "bsgp_state_layout",
             "bsgp_state_bytes", "bsgp_state_save", "bsgp_solve_resume", "bsgp_background2d",
             "bsgp_convolve2d", "bsgp_detect_sources", "bsgp_segment_catalog",
-            "bsgp_plan_set_static_geo", "bsgp_plan_static_geo"]
+            "bsgp_plan_set_static_geo", "bsgp_plan_static_geo", "bsgp_radial_profile",
+            "bsgp_fit_gauss1d", "bsgp_wasserstein1"]
 
 
 def check(rc):

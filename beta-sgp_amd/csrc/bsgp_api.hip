@@ -1680,6 +1680,72 @@ int bsgp_segment_catalog(const double* data, const double* conv, const int32_t* 
   return BSGP_OK;
 }
 
+int bsgp_radial_profile(const void* data, int32_t dtype, int32_t B, int32_t H, int32_t W,
+                        const double* centers, int32_t rcap, double* prof, int32_t* len,
+                        void* stream) {
+  if (!data) return fail(BSGP_ERR_ARG, "data is NULL");
+  if (!centers) return fail(BSGP_ERR_ARG, "centers is NULL");
+  if (!prof || !len) return fail(BSGP_ERR_ARG, "prof / len is NULL");
+  if (dtype != BSGP_DTYPE_F32 && dtype != BSGP_DTYPE_F64)
+    return fail(BSGP_ERR_ARG, "dtype must be BSGP_DTYPE_F32 or BSGP_DTYPE_F64");
+  if (B < 1 || H < 1 || W < 1) return fail(BSGP_ERR_ARG, "B, H and W must be >= 1");
+  if (rcap < 1) return fail(BSGP_ERR_ARG, "rcap must be >= 1");
+  char msg[160];
+  if ((int64_t)H * W > kStampMaxPixels) {
+    snprintf(msg, sizeof msg, "stamp of %lld pixels: a stamp holds at most %d (H * W <= %d)",
+             (long long)H * W, kStampMaxPixels, kStampMaxPixels);
+    return fail(BSGP_ERR_UNSUPPORTED, msg);
+  }
+  if (rcap > kStampMaxBins) {
+    snprintf(msg, sizeof msg, "%d radial bins: a profile holds at most %d", rcap, kStampMaxBins);
+    return fail(BSGP_ERR_UNSUPPORTED, msg);
+  }
+  StampProfArgs a{};
+  a.data = data, a.centers = centers, a.B = B, a.H = H, a.W = W, a.rcap = rcap;
+  a.prof = prof, a.len = len;
+  HIP_TRY(launch_stamp_radprof(a, dtype == BSGP_DTYPE_F32, (hipStream_t)stream));
+  return BSGP_OK;
+}
+
+int bsgp_fit_gauss1d(const double* prof, const int32_t* len, int32_t B, int32_t rcap,
+                     const double* fwhm, double* fitted, double* params, double* perr,
+                     int32_t* info, void* stream) {
+  if (!prof || !len || !fwhm) return fail(BSGP_ERR_ARG, "prof / len / fwhm is NULL");
+  if (!fitted || !params || !perr || !info)
+    return fail(BSGP_ERR_ARG, "fitted / params / perr / info is NULL");
+  if (B < 1 || rcap < 1) return fail(BSGP_ERR_ARG, "B and rcap must be >= 1");
+  if (rcap > kStampMaxBins) {
+    char msg[128];
+    snprintf(msg, sizeof msg, "profiles of %d values: a profile holds at most %d", rcap,
+             kStampMaxBins);
+    return fail(BSGP_ERR_UNSUPPORTED, msg);
+  }
+  StampFitArgs a{};
+  a.prof = prof, a.len = len, a.fwhm = fwhm, a.B = B, a.rcap = rcap;
+  a.fitted = fitted, a.params = params, a.perr = perr, a.info = info;
+  HIP_TRY(launch_stamp_fit(a, (hipStream_t)stream));
+  return BSGP_OK;
+}
+
+int bsgp_wasserstein1(const double* u, const int32_t* ulen, const double* v, const int32_t* vlen,
+                      int32_t B, int32_t rcap, double* out, void* stream) {
+  if (!u || !v) return fail(BSGP_ERR_ARG, "u / v is NULL");
+  if (!out) return fail(BSGP_ERR_ARG, "out is NULL");
+  if (B < 1 || rcap < 1) return fail(BSGP_ERR_ARG, "B and rcap must be >= 1");
+  if (rcap > kStampMaxBins) {
+    char msg[128];
+    snprintf(msg, sizeof msg, "samples of %d values: a sample holds at most %d", rcap,
+             kStampMaxBins);
+    return fail(BSGP_ERR_UNSUPPORTED, msg);
+  }
+  StampW1Args a{};
+  a.u = u, a.v = v, a.ulen = ulen, a.vlen = vlen, a.B = B, a.rcap = rcap, a.out = out;
+  a.P = 2;
+  while (a.P < 2 * rcap) a.P *= 2;
+  HIP_TRY(launch_stamp_w1(a, (hipStream_t)stream));
+  return BSGP_OK;
+}
+
 int bsgp_beta_div(int64_t n, const double* y, const double* x, double beta, double* out,
                   void* stream) {
   if (n < 1 || n > 0x7fffffff || !y || !x || !out) return fail(BSGP_ERR_ARG, "bad arguments");

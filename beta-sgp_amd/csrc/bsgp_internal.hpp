@@ -194,6 +194,33 @@ struct SegCatArgs {
 hipError_t launch_seg_convolve(const SegConvArgs& a, int f32, hipStream_t s);
 hipError_t launch_seg_detect(const SegArgs& a, int f32, hipStream_t s);
 hipError_t launch_seg_catalog(const SegCatArgs& a, hipStream_t s);
+// ---- star-stamp metrics (bsgp_stamps.hip) ----------------------
+constexpr int kStampMaxPixels = 16384;  // H * W of one stamp
+constexpr int kStampMaxBins = 256;      // radial bins / profile length / sample length
+struct StampProfArgs {
+  const void* data;       // [B][H][W] float32 or float64
+  const double* centers;  // [B][2]: (along rows, along columns)
+  int B, H, W, rcap;
+  double* prof;  // [B][rcap], NaN beyond an image's length
+  int* len;      // [B]: largest bin + 1
+};
+struct StampFitArgs {
+  const double* prof;  // [B][rcap]
+  const int* len;      // [B]
+  const double* fwhm;  // [B]
+  int B, rcap;
+  double *fitted, *params, *perr;  // [B][rcap], [B][3], [B][3]
+  int* info;                       // [B][2]: ier, nfev
+};
+struct StampW1Args {
+  const double *u, *v;     // [B][rcap]
+  const int *ulen, *vlen;  // [B], or nullptr: rcap
+  int B, rcap, P;          // P: power of two >= 2 rcap (the sort's size)
+  double* out;             // [B]
+};
+hipError_t launch_stamp_radprof(const StampProfArgs& a, int f32, hipStream_t s);
+hipError_t launch_stamp_fit(const StampFitArgs& a, hipStream_t s);
+hipError_t launch_stamp_w1(const StampW1Args& a, hipStream_t s);
 struct PsfModel;
 hipError_t launch_psf_stamps(const PsfModel& m, const double* xy, int n, int spatial,
                              int normalize, double* out, hipStream_t s);

@@ -444,6 +444,49 @@ int bsgp_segment_catalog(const double* data, const double* conv, const int32_t* 
                          int32_t* int_cols_out, double* f64_cols_out, int32_t* status_out,
                          void* stream);
 
+/* Star-stamp metrics: what application_sgp_star_stamps.py:117-142
+ * computes for the observed and the restored stamp.  All three are
+ * asynchronous; every image, profile and pair is processed on its own and gets
+ * the bits it gets alone.
+ *
+ * bsgp_radial_profile: utils.radial_profile (restoration/utils.py:81-92).
+ * r = (int)sqrt((i - c0)^2 + (j - c1)^2) with i the row and j the column:
+ * centers [B][2] (device float64) holds (c0, c1), and c0 is measured along the
+ * rows.  The reference passes (xcentroid, ycentroid) there; the quirk is kept.
+ * prof [B][rcap] = sum of the pixels of bin k, added in raster order, over
+ * their count (bit-equal to numpy.bincount's quotient; an empty bin is NaN),
+ * NaN from len[b] = largest r + 1 on.  rcap must be at least every image's
+ * length (the caller computes it from the shape and the centres, which must be
+ * finite); bins from rcap on are dropped.  data: float32 or float64 (dtype),
+ * widened first.  H * W <= 16384 and rcap <= 256, else BSGP_ERR_UNSUPPORTED. */
+int bsgp_radial_profile(const void* data, int32_t dtype, int32_t B, int32_t H, int32_t W,
+                        const double* centers, int32_t rcap, double* prof, int32_t* len,
+                        void* stream);
+/* utils.fit_radprof (utils.py:180-202): a * exp(-0.5 (x - m)^2 / s^2) fitted
+ * to (x = 0 .. len[b]-1, prof[b]) from a = 0.8 max(prof), m = 0, s = fwhm[b] /
+ * (2 sqrt(2 ln 2)) by MINPACK's lmder as scipy.optimize.leastsq calls it for
+ * astropy's LevMarLSQFitter: analytic Jacobian, ftol 1.49012e-8, xtol 1e-7,
+ * gtol 0, maxfev 100, factor 100, mode 1; s clipped below at float32's tiny in
+ * the residuals and the result, not in the Jacobian.  prof, fitted: [B][rcap]
+ * (fitted: the model at x, NaN from len[b] on); len, fwhm: [B]; params [B][3]
+ * = a, m, s; perr [B][3] = sqrt(|diag(cov_x sum(fvec^2) / (len - 3))|), NaN
+ * where leastsq gives no cov_x (singular R, exit code not 1..4) or len <= 3;
+ * info [B][2] = ier (MINPACK's info; 5 = maxfev), nfev.  len < 3, len > rcap or
+ * a non-finite value inside the length: ier 0, nfev 0 and NaN everywhere.
+ * rcap <= 256, else BSGP_ERR_UNSUPPORTED. */
+int bsgp_fit_gauss1d(const double* prof, const int32_t* len, int32_t B, int32_t rcap,
+                     const double* fwhm, double* fitted, double* params, double* perr,
+                     int32_t* info, void* stream);
+/* utils.wasserstein_distance_norm (utils.py:276-291), i.e.
+ * scipy.stats.wasserstein_distance(u[b][:ulen[b]], v[b][:vlen[b]]) without
+ * weights: the sum over the merged sorted values t of |#{u <= t} / n -
+ * #{v <= t} / m| dt, in ascending order.  u, v: [B][rcap] device float64;
+ * ulen, vlen: device int32 [B] (NULL: rcap); out [B].  A non-finite value
+ * inside a length, or a length outside 1..rcap, gives NaN.  rcap <= 256, else
+ * BSGP_ERR_UNSUPPORTED. */
+int bsgp_wasserstein1(const double* u, const int32_t* ulen, const double* v, const int32_t* vlen,
+                      int32_t B, int32_t rcap, double* out, void* stream);
+
 int bsgp_device_synchronize(void);
 const char* bsgp_last_error(void);
 /* The persistent solver's compile-time-geometry path (256 x 256 images on a
