@@ -34,6 +34,9 @@ BSGP_ERR_UNSUPPORTED = -3
 BSGP_ERR_PSF = -4
 BSGP_DTYPE_F32 = 0
 BSGP_DTYPE_F64 = 1
+BSGP_DEBLEND_MAX_BOX = 4096  # box pixels of one parent (include/bsgp.h)
+BSGP_DEBLEND_LINEAR, BSGP_DEBLEND_EXPONENTIAL = 0, 1
+BSGP_DEBLEND_OVER_CAP, BSGP_DEBLEND_BAD_LABEL = 1, 2
 
 
 class BsgpError(RuntimeError):
@@ -167,6 +170,8 @@ def lib():
             L.bsgp_detect_sources.argtypes = [vp, i32, i32, i32, i32, vp, dbl, i32, i32, vp, vp,
                                               vp, vp]
             L.bsgp_segment_catalog.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]
+            L.bsgp_deblend_sources.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp, i32, i32, dbl,
+                                               i32, i32, vp, vp, vp, vp]
             L.bsgp_radial_profile.argtypes = [vp, i32, i32, i32, i32, vp, i32, vp, vp, vp]
             L.bsgp_fit_gauss1d.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]
             L.bsgp_wasserstein1.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp]
@@ -181,7 +186,7 @@ def lib():
                          "bsgp_background2d", "bsgp_convolve2d", "bsgp_detect_sources",
                          "bsgp_segment_catalog", "bsgp_plan_set_static_geo",
                          "bsgp_plan_static_geo", "bsgp_radial_profile", "bsgp_fit_gauss1d",
-                         "bsgp_wasserstein1"]:
+                         "bsgp_wasserstein1", "bsgp_deblend_sources"]:
                 getattr(L, name).restype = ctypes.c_int
             if L.bsgp_abi_version() != ABI_VERSION:
                 raise BsgpError(-3, f"{LIB_PATH} has ABI {L.bsgp_abi_version()}, this binding "
@@ -198,7 +203,7 @@ EXPORTED = ["bsgp_plan_create", "bsgp_plan_create_checked", "bsgp_plan_destroy",
             "bsgp_state_bytes", "bsgp_state_save", "bsgp_solve_resume", "bsgp_background2d",
             "bsgp_convolve2d", "bsgp_detect_sources", "bsgp_segment_catalog",
             "bsgp_plan_set_static_geo", "bsgp_plan_static_geo", "bsgp_radial_profile",
-            "bsgp_fit_gauss1d", "bsgp_wasserstein1"]
+            "bsgp_fit_gauss1d", "bsgp_wasserstein1", "bsgp_deblend_sources"]
 
 
 def check(rc):

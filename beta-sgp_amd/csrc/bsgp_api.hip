@@ -1680,6 +1680,46 @@ int bsgp_segment_catalog(const double* data, const double* conv, const int32_t* 
   return BSGP_OK;
 }
 
+int bsgp_deblend_sources(const double* data, const int32_t* labels, int32_t B, int32_t H, int32_t W,
+                         int32_t cap, const int32_t* nlabels, const int32_t* int_cols,
+                         const uint8_t* select, int32_t npixels, int32_t nlevels, double contrast,
+                         int32_t mode, int32_t connectivity, int32_t* labels_out,
+                         int32_t* nlabels_out, int32_t* status_out, void* stream) {
+  if (!data) return fail(BSGP_ERR_ARG, "data is NULL");
+  if (!labels || !nlabels || !int_cols) return fail(BSGP_ERR_ARG, "labels / nlabels / int_cols is NULL");
+  if (!labels_out || !nlabels_out || !status_out)
+    return fail(BSGP_ERR_ARG, "labels_out / nlabels_out / status_out is NULL");
+  if (labels_out == labels) return fail(BSGP_ERR_ARG, "labels_out must not be labels");
+  if (cap < 1) return fail(BSGP_ERR_ARG, "cap must be >= 1");
+  if (npixels < 1) return fail(BSGP_ERR_ARG, "npixels must be >= 1");
+  if (nlevels < 1) return fail(BSGP_ERR_ARG, "nlevels must be >= 1");
+  if (!(contrast >= 0.0 && contrast <= 1.0)) return fail(BSGP_ERR_ARG, "contrast must lie in [0, 1]");
+  if (mode != BSGP_DEBLEND_LINEAR && mode != BSGP_DEBLEND_EXPONENTIAL)
+    return fail(BSGP_ERR_ARG, "mode must be BSGP_DEBLEND_LINEAR or BSGP_DEBLEND_EXPONENTIAL");
+  if (connectivity != 4 && connectivity != 8)
+    return fail(BSGP_ERR_ARG, "connectivity must be 4 or 8");
+  if (int rc = seg_shape(B, H, W)) return rc;
+  DeblendArgs a{};
+  a.data = data, a.labels = labels, a.nlabels = nlabels, a.icols = int_cols, a.sel = select;
+  a.B = B, a.H = H, a.W = W, a.cap = cap, a.npixels = npixels, a.nlevels = nlevels;
+  a.conn = connectivity, a.mode = mode, a.contrast = contrast;
+  a.labels_out = labels_out, a.nlabels_out = nlabels_out, a.status = status_out;
+  hipStream_t s = (hipStream_t)stream;
+  // stream-ordered workspace: the call stays asynchronous
+  const size_t rows = (size_t)B * cap;
+  void* w = nullptr;
+  HIP_TRY(hipMallocAsync(&w, 2 * rows * sizeof(int), s));
+  a.nchild = static_cast<int*>(w);
+  a.base = a.nchild + rows;
+  hipError_t e = hipMemsetAsync(a.nchild, 0, rows * sizeof(int), s);
+  if (e == hipSuccess) e = hipMemsetAsync(status_out, 0, (size_t)B * sizeof(int), s);
+  if (e == hipSuccess) e = launch_deblend(a, s);
+  const hipError_t ef = hipFreeAsync(w, s);
+  if (e != hipSuccess) return fail(BSGP_ERR_HIP, std::string("deblend launch: ") + hipGetErrorString(e));
+  HIP_TRY(ef);
+  return BSGP_OK;
+}
+
 int bsgp_radial_profile(const void* data, int32_t dtype, int32_t B, int32_t H, int32_t W,
                         const double* centers, int32_t rcap, double* prof, int32_t* len,
                         void* stream) {

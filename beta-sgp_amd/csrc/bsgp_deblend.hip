@@ -1,0 +1,464 @@
+// bsgp_deblend.hip — deblending of detected sources on the device: what
+// SourceFinder(deblend=True) adds to detect_sources in restoration/utils.py:235,
+// modelled on photutils' deblend_sources (multi-threshold tree + watershed) and
+// restated from its parts:
+//
+//  k_deblend_parent  one workgroup per parent segment.  The parent's box of
+//                    data and its mask are staged in LDS; D1 statistics by one
+//                    wave in a fixed lane order; per level (D3) a union-find
+//                    over the box in LDS with k_seg_union's neighbour tree
+//                    (root = smallest index, integer atomicMin only, areas by
+//                    integer atomicAdd); the marker tree (D4) by counting the
+//                    level's kept roots per current region (integer atomicAdd);
+//                    the flood (D5) on one lane with a binary heap in LDS keyed
+//                    by (-v, index); the contrast loop (D6) with one wave per
+//                    child summing in a fixed order.  Writes the parent's child
+//                    count and, for a split parent, every pixel's child rank
+//                    into labels_out.
+//  k_deblend_number  one workgroup per image: D7's numbering from the child
+//                    counts (two scans in label order).
+//  k_deblend_relabel one thread per pixel: the final int32 label image.
+//
+// No floating-point atomics, no kernel waits for another workgroup; a parent's
+// result depends only on its own pixels and box.
+#include <hip/hip_runtime.h>
+
+#include "bsgp_internal.hpp"
+
+namespace bsgp {
+
+namespace {
+
+constexpr int kBox = kDeblendMaxBox;
+constexpr int kOutside = -1;  // not a pixel of the parent
+constexpr int kFree = -2;     // a pixel of the parent in no region / not yet flooded
+
+__device__ __forceinline__ double db_inf() { return __longlong_as_double(0x7ff0000000000000LL); }
+
+__device__ __forceinline__ int db_load(const int* p) {
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
+// seg_find / seg_unite of bsgp_segment.hip on an LDS array
+__device__ __forceinline__ int db_find(int* L, int a) {
+  int p = db_load(L + a);
+  while (p != a) {
+    const int g = db_load(L + p);
+    if (g != p) atomicMin(L + a, g);
+    a = p;
+    p = g;
+  }
+  return a;
+}
+
+__device__ __forceinline__ void db_unite(int* L, int a, int b) {
+  for (;;) {
+    a = db_find(L, a);
+    b = db_find(L, b);
+    if (a == b) return;
+    if (a < b) {
+      const int t = a;
+      a = b;
+      b = t;
+    }
+    const int old = atomicMin(L + a, b);
+    if (old == a) return;
+    a = old;
+  }
+}
+
+// a table of kBox 16-bit counters, two per int (a count is at most kBox)
+__device__ __forceinline__ void t16_add(int* t, int i) { atomicAdd(t + (i >> 1), 1 << ((i & 1) << 4)); }
+__device__ __forceinline__ int t16_get(const int* t, int i) {
+  return (t[i >> 1] >> ((i & 1) << 4)) & 0xffff;
+}
+
+// neighbour k = 0..7 of box pixel p (row-major, NW first), or -1
+__device__ __forceinline__ int db_nbr(int p, int x, int y, int k, int bw, int bh, int conn) {
+  const int kk = k < 4 ? k : k + 1;
+  const int dy = kk / 3 - 1, dx = kk - (kk / 3) * 3 - 1;
+  if (conn == 4 && dx != 0 && dy != 0) return -1;
+  const int xx = x + dx, yy = y + dy;
+  if (xx < 0 || xx >= bw || yy < 0 || yy >= bh) return -1;
+  return p + dy * bw + dx;
+}
+
+// heap order: the larger value first (the smaller key -v), then the smaller index
+__device__ __forceinline__ bool db_before(const double* v, int a, int b) {
+  const double x = v[a], y = v[b];
+  return x > y || (x == y && a < b);
+}
+
+__device__ __forceinline__ void db_push(short* h, int& n, const double* v, int p) {
+  int i = n++;
+  while (i > 0) {
+    const int up = (i - 1) >> 1, q = h[up];
+    if (!db_before(v, p, q)) break;
+    h[i] = (short)q;
+    i = up;
+  }
+  h[i] = (short)p;
+}
+
+__device__ __forceinline__ int db_pop(short* h, int& n, const double* v) {
+  const int top = h[0], last = h[--n];
+  int i = 0;
+  for (;;) {
+    int c = 2 * i + 1;
+    if (c >= n) break;
+    int q = h[c];
+    if (c + 1 < n) {
+      const int q2 = h[c + 1];
+      if (db_before(v, q2, q)) {
+        ++c;
+        q = q2;
+      }
+    }
+    if (!db_before(v, q, last)) break;
+    h[i] = (short)q;
+    i = c;
+  }
+  h[i] = (short)last;
+  return top;
+}
+
+// D5 on the calling lane: lab holds a marker identity (>= 0), kFree or
+// kOutside per box pixel.  A labelled pixel without a free neighbour can give
+// its label to nobody, now or later, so it is not entered; every pixel enters
+// the heap at most once, so the heap holds at most the box.
+__device__ __forceinline__ void db_flood(const double* v, int* lab, short* heap, int bw, int bh,
+                                         int conn) {
+  int hn = 0;
+  for (int y = 0, p = 0; y < bh; ++y) {
+    for (int x = 0; x < bw; ++x, ++p) {
+      if (lab[p] < 0) continue;
+      bool open = false;
+      for (int k = 0; k < 8; ++k) {
+        const int q = db_nbr(p, x, y, k, bw, bh, conn);
+        if (q >= 0 && lab[q] == kFree) open = true;
+      }
+      if (open) db_push(heap, hn, v, p);
+    }
+  }
+  while (hn > 0) {
+    const int p = db_pop(heap, hn, v);
+    const int y = p / bw, x = p - y * bw, l = lab[p];
+    for (int k = 0; k < 8; ++k) {
+      const int q = db_nbr(p, x, y, k, bw, bh, conn);
+      if (q >= 0 && lab[q] == kFree) {
+        lab[q] = l;
+        db_push(heap, hn, v, q);
+      }
+    }
+  }
+}
+
+// sum of v over the box pixels with lab == want by the calling wave: lane
+// partials in raster order, one fixed-order wave reduction
+__device__ __forceinline__ double db_wave_sum_of(const double* v, const int* lab, int want, int n) {
+  const int lane = threadIdx.x & 63;
+  double s = 0.0;
+  for (int k = lane; k < n; k += 64)
+    if (lab[k] == want) s += v[k];
+  return wave_sum(s);
+}
+
+// the workgroup scan of bsgp_segment.hip
+__device__ __forceinline__ int db_block_scan(int c, int* wsum, int* total) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  int inc = c;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int u = __shfl_up(inc, o, 64);
+    if (lane >= o) inc += u;
+  }
+  if (lane == 63) wsum[w] = inc;
+  __syncthreads();
+  int base = 0, tot = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int u = wsum[k];
+    if (k < w) base += u;
+    tot += u;
+  }
+  __syncthreads();
+  *total = tot;
+  return base + inc - c;
+}
+
+__device__ __forceinline__ int db_rows(const DeblendArgs& a, int b) {
+  const int m = a.nlabels[b];
+  return m < a.cap ? (m < 0 ? 0 : m) : a.cap;
+}
+
+}  // namespace
+
+__global__ void __launch_bounds__(256) k_deblend_parent(DeblendArgs a) {
+  __shared__ double v[kBox];
+  __shared__ int lev[kBox];    // D3: union-find parents of the level; D5: flood labels
+  __shared__ short reg[kBox];  // the region (its root) a pixel is in, kFree or kOutside
+  __shared__ int bufA[kBox / 2];  // D3: areas (16-bit); then the marker list (shorts)
+  __shared__ int bufB[kBox / 2];  // D4: kept roots per region (16-bit); the heap; the ranks
+  __shared__ double thr[256];  // D2: thresholds of 256 levels
+  __shared__ double sred[8];
+  __shared__ int sint[8];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int i = blockIdx.x, b = blockIdx.y;
+  if (i >= db_rows(a, b)) return;
+  const size_t row = (size_t)b * a.cap + i;
+  const int* ic = a.icols + row * 5;
+  const int area = ic[0];
+  if (area <= 0 || area < 2 * (long long)a.npixels || (a.sel && !a.sel[row])) return;
+  const int x0 = ic[1], y0 = ic[3], bw = ic[2] - x0 + 1, bh = ic[4] - y0 + 1;
+  if (x0 < 0 || y0 < 0 || bw < 1 || bh < 1 || ic[2] >= a.W || ic[4] >= a.H) return;
+  if ((long long)bw * bh > kBox) {
+    if (tid == 0) atomicOr(a.status + b, BSGP_DEBLEND_OVER_CAP);
+    return;
+  }
+  const int n = bw * bh, want = i + 1;
+  const size_t o = (size_t)b * a.H * a.W;
+
+  // staging
+  if (tid == 0) sint[0] = n, sint[1] = 0, sint[5] = 0;
+  __syncthreads();
+  for (int k = tid; k < n; k += 256) {
+    const int r = k / bw, c = k - r * bw;
+    const size_t q = o + (size_t)(y0 + r) * a.W + (x0 + c);
+    const bool in = a.labels[q] == want;
+    v[k] = a.data[q];
+    reg[k] = in ? 0 : kOutside;
+    if (in) atomicMin(&sint[0], k);
+  }
+  __syncthreads();
+  const int root0 = sint[0];
+  if (root0 >= n) return;
+  for (int k = tid; k < n; k += 256)
+    if (reg[k] != kOutside) reg[k] = (short)root0;
+  __syncthreads();
+
+  // D1
+  if (wave == 0) {
+    double s = 0.0, mn = db_inf(), mx = -db_inf();
+    for (int k = lane; k < n; k += 64) {
+      if (reg[k] == kOutside) continue;
+      const double x = v[k];
+      s += x;
+      mn = x < mn ? x : mn;
+      mx = x > mx ? x : mx;
+    }
+    s = wave_sum(s);
+    mn = wave_min(mn);
+    mx = wave_max(mx);
+    if (lane == 0) sred[0] = mn, sred[1] = mx, sred[2] = s;
+  }
+  __syncthreads();
+  const double smin = sred[0], smax = sred[1], ssum = sred[2];
+  if (!(smin < smax)) return;
+
+  // D2 to D4
+  const bool linear = a.mode == BSGP_DEBLEND_LINEAR || smin < 0.0;
+  const double m = smin != 0.0 ? smin : 0.01 * smax;
+  const double den = (double)(a.nlevels + 1);
+  const int half = (n + 1) >> 1;
+  for (int lv = 1; lv <= a.nlevels; ++lv) {
+    // the next 256 thresholds, one per thread (a pow per level and wave would
+    // cost as much as the level's labelling); the last level ended at a barrier
+    if (((lv - 1) & 255) == 0) {
+      const double k = (double)(lv + tid);
+      thr[tid] = linear ? smin + (smax - smin) / den * k : m * pow(smax / m, k / den);
+      __syncthreads();
+    }
+    const double t = thr[(lv - 1) & 255];
+    int above = 0;
+    for (int p = tid; p < n; p += 256) {
+      const bool on = reg[p] != kOutside && v[p] > t;
+      lev[p] = on ? p : -1;
+      above += on;
+    }
+    if (above) atomicAdd(&sint[5], above);
+    for (int j = tid; j < half; j += 256) bufA[j] = 0, bufB[j] = 0;
+    __syncthreads();
+    // two components of npixels pixels need 2 * npixels pixels above the
+    // level, and the levels rise: nothing can split from here on
+    if (sint[5] < 2 * (long long)a.npixels) break;
+    for (int p = tid; p < n; p += 256) {
+      if (db_load(lev + p) < 0) continue;
+      const int y = p / bw, x = p - y * bw, q = p - bw;
+      const bool w = x > 0 && db_load(lev + p - 1) >= 0;
+      const bool nn = y > 0 && db_load(lev + q) >= 0;
+      if (a.conn == 4) {
+        if (w) db_unite(lev, p, p - 1);
+        if (nn) db_unite(lev, p, q);
+        continue;
+      }
+      if (nn) {
+        db_unite(lev, p, q);
+        continue;
+      }
+      const bool nw = y > 0 && x > 0 && db_load(lev + q - 1) >= 0;
+      const bool ne = y > 0 && x < bw - 1 && db_load(lev + q + 1) >= 0;
+      if (ne) db_unite(lev, p, q + 1);
+      if (nw) db_unite(lev, p, q - 1);
+      else if (w) db_unite(lev, p, p - 1);
+    }
+    __syncthreads();
+    for (int p = tid; p < n; p += 256) {
+      if (db_load(lev + p) < 0) continue;
+      const int r = db_find(lev, p);
+      if (r != p) __hip_atomic_store(lev + p, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      t16_add(bufA, r);
+    }
+    if (tid == 0) sint[5] = 0;  // every thread read it before the barrier above
+    __syncthreads();
+    // a kept component lies inside one region: count it there
+    for (int p = tid; p < n; p += 256)
+      if (lev[p] == p && t16_get(bufA, p) >= a.npixels && reg[p] >= 0) t16_add(bufB, reg[p]);
+    __syncthreads();
+    // a region holding two or more is replaced by them
+    for (int p = tid; p < n; p += 256) {
+      const int R = reg[p];
+      if (R < 0 || t16_get(bufB, R) < 2) continue;
+      const int l = lev[p];
+      reg[p] = (l >= 0 && t16_get(bufA, l) >= a.npixels) ? (short)l : (short)kFree;
+      sint[1] = 1;
+    }
+    __syncthreads();
+  }
+  if (!sint[1]) return;
+
+  // the markers, in raster order
+  short* mk = reinterpret_cast<short*>(bufA);
+  short* hp = reinterpret_cast<short*>(bufB);
+  for (int p = tid; p < n; p += 256) lev[p] = reg[p];
+  if (wave == 0) {
+    int nm = 0;
+    for (int base = 0; base < n; base += 64) {
+      const int p = base + lane;
+      const bool f = p < n && reg[p] == p;
+      const unsigned long long bal = __ballot(f);
+      if (f) mk[nm + __popcll(bal & ((1ull << lane) - 1ull))] = (short)p;
+      nm += __popcll(bal);
+    }
+    if (lane == 0) sint[2] = nm;
+  }
+  __syncthreads();
+  const int nm = sint[2];
+  int alive = nm;
+
+  // D5, D6
+  for (;;) {
+    if (tid == 0) {
+      db_flood(v, lev, hp, bw, bh, a.conn);
+      sint[3] = 0;
+    }
+    __syncthreads();
+    double bf = db_inf();
+    int bc = 0x7fffffff, below = 0;
+    for (int ci = wave; ci < nm; ci += 4) {
+      const int c = mk[ci];
+      if (c < 0) continue;
+      const double frac = db_wave_sum_of(v, lev, c, n) / ssum;
+      if (frac < a.contrast) below = 1;
+      if (frac < bf || (frac == bf && c < bc)) bf = frac, bc = c;
+    }
+    if (lane == 0) {
+      sred[4 + wave] = bf, sint[4 + wave] = bc;
+      if (below) atomicOr(&sint[3], 1);
+    }
+    __syncthreads();
+    if (!sint[3]) break;
+    bf = sred[4], bc = sint[4];
+    for (int k = 1; k < 4; ++k) {
+      const double f = sred[4 + k];
+      const int c = sint[4 + k];
+      if (f < bf || (f == bf && c < bc)) bf = f, bc = c;
+    }
+    for (int p = tid; p < n; p += 256)
+      if (lev[p] == bc) lev[p] = kFree;
+    for (int ci = tid; ci < nm; ci += 256)
+      if (mk[ci] == bc) mk[ci] = -1;
+    --alive;
+    __syncthreads();
+    if (alive < 2) break;  // one child or none: the parent stays
+  }
+  if (alive < 2) return;
+
+  // child ranks in marker order, into labels_out (k_deblend_relabel adds the base)
+  if (wave == 0) {
+    int r = 0;
+    for (int base = 0; base < nm; base += 64) {
+      const int ci = base + lane;
+      const int c = ci < nm ? mk[ci] : -1;
+      const unsigned long long bal = __ballot(c >= 0);
+      if (c >= 0) hp[c] = (short)(r + __popcll(bal & ((1ull << lane) - 1ull)));
+      r += __popcll(bal);
+    }
+  }
+  __syncthreads();
+  for (int k = tid; k < n; k += 256) {
+    const int l = lev[k];
+    if (l == kOutside) continue;
+    const int r = k / bw, c = k - r * bw;
+    // a pixel the flood did not reach (connectivity 4 inside an 8-connected
+    // parent) is dropped, as the watershed leaves it 0
+    a.labels_out[o + (size_t)(y0 + r) * a.W + (x0 + c)] = l >= 0 ? hp[l] : -1;
+  }
+  if (tid == 0) a.nchild[row] = alive;
+}
+
+// D7: parents left as they are first, in label order, then the children by parent
+__global__ void __launch_bounds__(256) k_deblend_number(DeblendArgs a) {
+  __shared__ int wsum[4];
+  const int b = blockIdx.x, n = db_rows(a, b);
+  const size_t row0 = (size_t)b * a.cap;
+  int cu = 0, cc = 0;
+  for (int base = 0; base < n; base += 256) {
+    const int i = base + threadIdx.x;
+    const bool valid = i < n && a.icols[(row0 + i) * 5] > 0;
+    const int c = valid ? a.nchild[row0 + i] : 0;
+    const int u = valid && c == 0;
+    int tu, tc;
+    const int eu = db_block_scan(u, wsum, &tu), ec = db_block_scan(c, wsum, &tc);
+    if (i < n) a.base[row0 + i] = !valid ? 0 : (u ? cu + eu + 1 : cc + ec);
+    cu += tu;
+    cc += tc;
+  }
+  for (int i = threadIdx.x; i < n; i += 256)
+    if (a.nchild[row0 + i] > 0) a.base[row0 + i] += cu + 1;
+  if (threadIdx.x == 0) a.nlabels_out[b] = cu + cc;
+}
+
+__global__ void __launch_bounds__(256) k_deblend_relabel(DeblendArgs a) {
+  const int hw = a.H * a.W;
+  const unsigned pu = blockIdx.x * 256u + threadIdx.x;
+  if (pu >= (unsigned)hw) return;
+  const int b = blockIdx.y;
+  const size_t q = (size_t)b * hw + pu;
+  const int l = a.labels[q];
+  int out = 0;
+  if (l < 0 || l > db_rows(a, b)) {
+    atomicOr(a.status + b, BSGP_DEBLEND_BAD_LABEL);
+  } else if (l > 0) {
+    const size_t row = (size_t)b * a.cap + (l - 1);
+    const int base = a.base[row];
+    if (a.nchild[row] == 0) {
+      out = base;
+    } else {
+      const int r = a.labels_out[q];
+      out = r < 0 ? 0 : base + r;
+    }
+  }
+  a.labels_out[q] = out;
+}
+
+hipError_t launch_deblend(const DeblendArgs& a, hipStream_t s) {
+  const int hw = a.H * a.W;
+  const dim3 block(256);
+  hipLaunchKernelGGL(k_deblend_parent, dim3(a.cap, a.B), block, 0, s, a);
+  hipLaunchKernelGGL(k_deblend_number, dim3(a.B), block, 0, s, a);
+  hipLaunchKernelGGL(k_deblend_relabel, dim3((unsigned)(((size_t)hw + 255) / 256), a.B), block, 0,
+                     s, a);
+  return hipGetLastError();
+}
+
+}  // namespace bsgp

@@ -194,6 +194,23 @@ struct SegCatArgs {
 hipError_t launch_seg_convolve(const SegConvArgs& a, int f32, hipStream_t s);
 hipError_t launch_seg_detect(const SegArgs& a, int f32, hipStream_t s);
 hipError_t launch_seg_catalog(const SegCatArgs& a, hipStream_t s);
+// ---- deblending (bsgp_deblend.hip) -----------------------------
+constexpr int kDeblendMaxBox = BSGP_DEBLEND_MAX_BOX;  // box pixels of one parent (LDS)
+struct DeblendArgs {
+  const double* data;        // [B][H][W]
+  const int* labels;         // [B][H][W]
+  const int* nlabels;        // [B]
+  const int* icols;          // [B][cap][5] as bsgp_segment_catalog writes them
+  const unsigned char* sel;  // [B][cap], nonzero = deblend this label, or nullptr: all
+  int B, H, W, cap, npixels, nlevels, conn, mode;
+  double contrast;
+  int* nchild;       // workspace [B][cap]: children of a split parent, else 0 (zeroed first)
+  int* base;         // workspace [B][cap]: a parent's output label / its first child's
+  int* labels_out;   // [B][H][W]: child ranks of split parents, then the final labels
+  int* nlabels_out;  // [B]
+  int* status;       // [B]: BSGP_DEBLEND_* bits (zeroed first)
+};
+hipError_t launch_deblend(const DeblendArgs& a, hipStream_t s);
 // ---- star-stamp metrics (bsgp_stamps.hip) ----------------------
 constexpr int kStampMaxPixels = 16384;  // H * W of one stamp
 constexpr int kStampMaxBins = 256;      // radial bins / profile length / sample length

@@ -14,12 +14,16 @@ in DESIGN §3.8) and keeps photutils' names.
 What is pinned and what is not: the kernel equals astropy's at rtol 1e-13, the
 convolution equals astropy's to the last bit, the label image equals ``scipy.ndimage.label`` followed by the
 removal of small components and a consecutive relabel, which is photutils'
-``detect_sources``.  Deblending (``SourceFinder(deblend=True)``) is not done: it
-splits a segment among children without dropping a pixel, so the sum of
-``segment_flux`` over all segments -- the only quantity the application uses --
-is the same with and without it, while the per-segment columns here describe
-undeblended segments.  The moment and shape columns are defined in DESIGN
-§3.8, modelled on photutils' documentation but not pinned to it.
+``detect_sources``.  Deblending (``SourceFinder(deblend=True)``,
+:func:`deblend_sources`, ``bsgp_deblend_sources``) is modelled on photutils'
+documented ``deblend_sources`` and pinned to the parts it is built from,
+``scipy.ndimage.label`` and ``skimage.segmentation.watershed`` (DESIGN §3.8,
+steps D1 to D7).  It splits a segment among children without dropping a pixel,
+so the sum of ``segment_flux`` over all segments -- the quantity the flux
+constraint and the score use -- is the same with and without it;
+``source_info`` therefore deblends only on request (``deblend=True``), for the
+per-source columns.  The moment and shape columns are defined in DESIGN §3.8,
+modelled on photutils' documentation but not pinned to it.
 """
 import warnings
 
@@ -45,6 +49,15 @@ UNAVAILABLE = {
 
 class NoDetectionsWarning(UserWarning):
     """No source was found (photutils' warning of the same name)."""
+
+
+class DeblendBoxWarning(UserWarning):
+    """A parent segment's bounding box holds more than DEBLEND_MAX_BOX pixels:
+    it is left undeblended."""
+
+
+DEBLEND_MAX_BOX = _B.BSGP_DEBLEND_MAX_BOX
+DEBLEND_MODES = {"linear": _B.BSGP_DEBLEND_LINEAR, "exponential": _B.BSGP_DEBLEND_EXPONENTIAL}
 
 
 def make_2dgaussian_kernel(fwhm, size, mode="oversample", oversample=10):
@@ -152,12 +165,17 @@ class SegmentationImage:
     """Result of :func:`detect_sources`: ``data`` (int32 label image, 0 =
     background), ``nlabels``, ``labels`` (1..nlabels) and ``areas`` (pixels per
     label).  For a batch ``data`` is [B, H, W], ``nlabels`` an int array [B]
-    and ``labels`` / ``areas`` lists of B arrays."""
+    and ``labels`` / ``areas`` lists of B arrays.  The result of
+    :func:`deblend_sources` also carries ``parent``, per label the label of the
+    input segment it came from, and ``status``, the ``BSGP_DEBLEND_*`` bits the
+    device set per image (both ``None`` otherwise)."""
 
-    def __init__(self, data, nlabels, batched):
+    def __init__(self, data, nlabels, batched, parent=None, status=None):
         self.data, self.batched = data, batched
         self.nlabels = nlabels if batched else int(nlabels[0])
         self._n = np.asarray(nlabels)
+        self.parent = parent if parent is None or batched else parent[0]
+        self.status = status if status is None or batched else int(status[0])
 
     @property
     def labels(self):
@@ -229,6 +247,189 @@ def _detect_dev(d, threshold, npixels, connectivity, mask):
     return lab, n.cpu().numpy()  # waits for the kernels (d, thr_map, m are alive until here)
 
 
+def check_deblend_args(shape, seg_shape, npixels, nlevels=32, contrast=0.001, mode="exponential",
+                       connectivity=8, relabel=True):
+    """The argument checks of deblend_sources (host only)."""
+    _check_image_shape(shape)
+    if tuple(seg_shape) != tuple(shape):
+        raise ValueError(f"segment_img shape {tuple(seg_shape)} does not match data shape "
+                         f"{tuple(shape)}")
+    if int(npixels) != npixels or npixels < 1:
+        raise ValueError(f"npixels must be a positive int, got {npixels!r}")
+    if int(nlevels) != nlevels or nlevels < 1:
+        raise ValueError(f"nlevels must be a positive int, got {nlevels!r}")
+    if not 0.0 <= contrast <= 1.0:
+        raise ValueError(f"contrast must lie in [0, 1], got {contrast!r}")
+    if mode == "sinh":
+        raise ValueError("mode 'sinh' is not offered: use 'exponential' or 'linear'")
+    if mode not in DEBLEND_MODES:
+        raise ValueError(f"mode must be 'exponential' or 'linear', got {mode!r}")
+    if connectivity not in (4, 8):
+        raise ValueError(f"connectivity must be 4 or 8, got {connectivity!r}")
+    if not relabel:
+        raise ValueError("relabel=False is not offered: the output labels are consecutive")
+
+
+def deblend_numbering(nchild, present=None):
+    """D7 on the host (the rule k_deblend_number implements): from the number of
+    children per input label 1..n (0 = left as it is) the output label of every
+    parent left as it is, the first child's label of every split parent, and
+    the number of output labels.  ``present``: labels the image holds."""
+    nchild = np.asarray(nchild, dtype=np.int64)
+    present = np.ones(len(nchild), bool) if present is None else np.asarray(present, bool)
+    kept = present & (nchild == 0)
+    kids = np.where(present, nchild, 0)
+    base = np.zeros(len(nchild), dtype=np.int64)
+    base[kept] = np.arange(1, kept.sum() + 1)
+    first = kept.sum() + 1 + np.cumsum(kids) - kids
+    base[kids > 0] = first[kids > 0]
+    return base, int(kept.sum() + kids.sum())
+
+
+def _deblend_dev(d, lab, n, npixels, nlevels, contrast, mode, connectivity, select=None):
+    """(int32 CUDA labels [B, H, W], host nlabels [B], host status [B], int32
+    CUDA parents [B, max nlabels + 1]) of the deblended image; one wait for the
+    kernels.  d: float64 CUDA [B, H, W]; lab: int32 CUDA; n: host
+    int32 [B]; select: host bool [B, cap] or None."""
+    torch = _B.torch
+    B, H, W = d.shape
+    n = np.ascontiguousarray(n, dtype=np.int32)
+    cap = max(1, int(n.max()))
+    nd = torch.from_numpy(n).to("cuda")
+    ic = torch.empty((B, cap, 5), dtype=torch.int32, device="cuda")
+    fc = torch.empty((B, cap, 8), dtype=torch.float64, device="cuda")
+    st = torch.empty((B,), dtype=torch.int32, device="cuda")
+    _B.check(_B.lib().bsgp_segment_catalog(_B._ptr(d), None, _B._ptr(lab), B, H, W, cap, _B._ptr(nd),
+                                           _B._ptr(ic), _B._ptr(fc), _B._ptr(st),
+                                           _B.current_stream()))
+    sel = None
+    if select is not None:
+        sel = torch.from_numpy(np.ascontiguousarray(select, dtype=np.uint8)).to("cuda")
+    out = torch.empty((B, H, W), dtype=torch.int32, device="cuda")
+    nout = torch.empty((B,), dtype=torch.int32, device="cuda")
+    dst = torch.empty((B,), dtype=torch.int32, device="cuda")
+    _B.check(_B.lib().bsgp_deblend_sources(_B._ptr(d), _B._ptr(lab), B, H, W, cap, _B._ptr(nd),
+                                           _B._ptr(ic), _B._ptr(sel), int(npixels), int(nlevels),
+                                           float(contrast), DEBLEND_MODES[mode], int(connectivity),
+                                           _B._ptr(out), _B._ptr(nout), _B._ptr(dst),
+                                           _B.current_stream()))
+    # the count for the warning, by the kernel's own rule; which images hold such a parent is
+    # the kernel's status bit, and the two must agree
+    box = (ic[..., 2] - ic[..., 1] + 1).long() * (ic[..., 4] - ic[..., 3] + 1).long()
+    over = (ic[..., 0] >= 2 * int(npixels)) & (box > DEBLEND_MAX_BOX)
+    over &= torch.arange(cap, device="cuda")[None, :] < nd[:, None]
+    if sel is not None:
+        over &= sel != 0
+    host = torch.stack([nout, dst, st, over.sum(dim=1).to(torch.int32)]).cpu().numpy()
+    nout_h, status, cat_status, nover = host[0].astype(np.int32), host[1], host[2], host[3]
+    if cat_status.any() or (status & _B.BSGP_DEBLEND_BAD_LABEL).any():
+        bad = np.flatnonzero(cat_status | (status & _B.BSGP_DEBLEND_BAD_LABEL))
+        raise _B.BsgpError(_B.BSGP_ERR_ARG, f"image {int(bad[0])}: labels outside 1..nlabels in "
+                           "the segmentation image")
+    flagged = (status & _B.BSGP_DEBLEND_OVER_CAP) != 0
+    if not np.array_equal(flagged, nover > 0):
+        raise _B.BsgpError(_B.BSGP_ERR_HIP, "bsgp_deblend_sources reports parents over the box cap "
+                           f"in images {np.flatnonzero(flagged).tolist()}, int_cols hold them in "
+                           f"images {np.flatnonzero(nover > 0).tolist()}")
+    if flagged.any():
+        warnings.warn(f"{int(nover[flagged].sum())} parent segment(s) with a bounding box of more "
+                      f"than {DEBLEND_MAX_BOX} pixels were left undeblended", DeblendBoxWarning)
+    # parent of every output label: every pixel of a label writes the same input label
+    par = torch.zeros((B, int(nout_h.max()) + 1), dtype=torch.int32, device="cuda")
+    par.scatter_(1, out.reshape(B, -1).long(), lab.reshape(B, -1))
+    return out, nout_h, status.astype(np.int32), par
+
+
+def _deblended_image(res, batched, device_out):
+    """The SegmentationImage of _deblend_dev's result."""
+    out, n, status, par = res
+    par = par if device_out else par.cpu().numpy()
+    return SegmentationImage(_out(out, batched, device_out), n, batched,
+                             parent=[par[b, 1:k + 1] for b, k in enumerate(n)], status=status)
+
+
+def _labels_dev(segment_img, batched):
+    """(int32 CUDA labels [B, H, W], host nlabels [B]) of a SegmentationImage or
+    a label image."""
+    torch = _B.torch
+    seg = segment_img.data if isinstance(segment_img, SegmentationImage) else segment_img
+    lab = seg if torch.is_tensor(seg) else torch.from_numpy(np.ascontiguousarray(seg))
+    lab = lab.to(device="cuda", dtype=torch.int32).contiguous()
+    lab = lab if batched else lab[None]
+    if isinstance(segment_img, SegmentationImage):
+        return lab, np.asarray(segment_img._n, dtype=np.int32)
+    if bool((lab < 0).any()):
+        raise ValueError("segment_img holds negative labels")
+    return lab, lab.reshape(lab.shape[0], -1).amax(dim=1).cpu().numpy().astype(np.int32)
+
+
+def deblend_sources(data, segment_img, npixels, labels=None, nlevels=32, contrast=0.001,
+                    mode="exponential", connectivity=8, relabel=True, device_out=False):
+    """photutils' ``deblend_sources`` for an image or a batch: every segment of
+    ``segment_img`` (a :class:`SegmentationImage` or an integer label image) is
+    split by multi-thresholding (``nlevels`` levels between its minimum and
+    maximum of ``data``, spaced by ``mode`` 'exponential' or 'linear';
+    components of at least ``npixels`` pixels) and a watershed, and children
+    below ``contrast`` of the segment's flux are merged back (DESIGN §3.8, D1
+    to D7).  ``data`` is the image the segments were detected in (the
+    convolved one in ``source_info``).  ``labels``: deblend only these labels
+    (of every image of a batch that holds them; 1..max ``nlabels``).  Returns a :class:`SegmentationImage` with
+    consecutive labels -- the segments left as they are first, in their order,
+    then the children by parent -- that also carries ``parent`` and ``status``
+    (CUDA tensors with ``device_out=True``).  A segment
+    whose bounding box holds more than ``DEBLEND_MAX_BOX`` pixels is left as it
+    is, with one :class:`DeblendBoxWarning` per call.  ``mode='sinh'`` and
+    ``relabel=False`` raise ``ValueError``."""
+    seg = segment_img.data if isinstance(segment_img, SegmentationImage) else segment_img
+    check_deblend_args(_shape_of(data), _shape_of(seg), npixels, nlevels, contrast, mode,
+                       connectivity, relabel)
+    _B.require_gpu()
+    d, batched = _to_dev(data, keep_f32=False)
+    lab, n = _labels_dev(segment_img, batched)
+    select = None
+    if labels is not None:
+        want = np.atleast_1d(np.asarray(labels)).astype(np.int64)
+        top = int(n.max()) if batched else int(n[0])
+        if want.size and (want.min() < 1 or want.max() > top):
+            raise ValueError(f"labels must lie in 1..{top}, got {labels!r}")
+        select = np.zeros((d.shape[0], max(1, int(n.max()))), dtype=bool)
+        select[:, want - 1] = True  # an image of a batch without such a label has no such row
+    res = _deblend_dev(d, lab, n, npixels, nlevels, contrast, mode, connectivity, select)
+    return _deblended_image(res, batched, device_out)
+
+
+class SourceFinder:
+    """photutils' ``SourceFinder(npixels, connectivity=8, deblend=True, nlevels=32,
+    contrast=0.001, mode='exponential')`` as ``utils.source_info`` builds it
+    (restoration/utils.py:235): ``finder(data, threshold, mask=None)`` is
+    :func:`detect_sources` followed, when ``deblend``, by
+    :func:`deblend_sources`.  ``relabel``, ``nproc`` and ``progress_bar`` are
+    accepted for the signature; ``nproc`` and ``progress_bar`` are ignored."""
+
+    def __init__(self, npixels, connectivity=8, deblend=True, nlevels=32, contrast=0.001,
+                 mode="exponential", relabel=True, nproc=1, progress_bar=True, device_out=False):
+        check_detect_args((1, 1), npixels, connectivity)
+        check_deblend_args((1, 1), (1, 1), npixels, nlevels, contrast, mode, connectivity, relabel)
+        self.npixels, self.connectivity, self.deblend = int(npixels), int(connectivity), bool(deblend)
+        self.nlevels, self.contrast, self.mode = int(nlevels), float(contrast), mode
+        self.device_out = device_out
+
+    def __call__(self, data, threshold, mask=None):
+        check_detect_args(_shape_of(data), self.npixels, self.connectivity, _shape_of(threshold),
+                          None if mask is None else _shape_of(mask))
+        _B.require_gpu()
+        d, batched = _to_dev(data)
+        lab, n = _detect_dev(d, threshold, self.npixels, self.connectivity, mask)
+        if not batched and n[0] == 0:
+            warnings.warn("No sources were found.", NoDetectionsWarning)
+            return None
+        if self.deblend:
+            return _deblended_image(_deblend_dev(d.to(_B.torch.float64), lab, n, self.npixels,
+                                                 self.nlevels, self.contrast, self.mode,
+                                                 self.connectivity), batched, self.device_out)
+        return SegmentationImage(_out(lab, batched, self.device_out), n, batched)
+
+
 def shape_columns(sigx2, sigxy, sigy2):
     """The shape columns from the covariance of a segment's convolved pixels,
     by the formulas of photutils' documentation: a^2 and b^2 are the
@@ -262,8 +463,8 @@ class SourceCatalog:
     ``semiminor_sigma``, ``orientation`` (degrees), ``eccentricity``,
     ``ellipticity``, ``fwhm`` (:func:`shape_columns`).  ``segment_flux_sum`` is
     the sum over all segments -- the deblend-invariant quantity the
-    application uses -- per image.  The columns describe undeblended segments;
-    the moment and shape columns are modelled on photutils, not pinned to it.
+    application uses -- per image.  The columns describe the segments of
+    ``segment_img``, deblended or not; the moment and shape columns are modelled on photutils, not pinned to it.
     ``sky_centroid``, ``local_background`` and ``segment_fluxerr`` raise
     ``KeyError`` with the reason.  ``device_out=True`` adds ``int_cols`` /
     ``f64_cols`` (CUDA tensors [B, cap, 5] / [B, cap, 8])."""
@@ -349,13 +550,19 @@ class SourceCatalog:
         return {k: self[k] for k in (COLUMNS if columns is None else columns)}
 
 
-def source_info(data, box_size, n_pixels=5, sigma_threshold=1.5, device_out=False):
-    """``utils.source_info`` (restoration/utils.py:235-247) without the
-    deblending, for an image or a batch: ``Background2D(data, box_size,
+def source_info(data, box_size, n_pixels=5, sigma_threshold=1.5, device_out=False, deblend=False,
+                nlevels=32, contrast=0.001):
+    """``utils.source_info`` (restoration/utils.py:235-247) for an image or a
+    batch, with its deblending on request: ``Background2D(data, box_size,
     filter_size=(3, 3))``, ``sub = data - background``, ``threshold =
     sigma_threshold * background_rms``, ``conv = convolve(sub,
     make_2dgaussian_kernel(1.2, 3))``, ``detect_sources(conv, threshold,
-    n_pixels)`` and the catalogue of ``sub`` with ``convolved_data=conv``.
+    n_pixels)``, with ``deblend=True`` the reference's
+    ``SourceFinder(npixels=n_pixels, deblend=True)``, i.e. ``deblend_sources(conv,
+    segment_img, n_pixels, nlevels=nlevels, contrast=contrast)`` (connectivity 8,
+    mode 'exponential'), and the catalogue of ``sub`` with
+    ``convolved_data=conv``.  The default ``deblend=False`` gives the same sum
+    of ``segment_flux`` and the columns of undeblended segments.
     Returns ``(catalog, bkg)``; the catalogue also carries ``segment_img``,
     ``data`` (sub) and ``convolved_data``.  An unbatched image without a
     detection warns and gives ``(None, bkg)``.  With ``device_out=True`` the
@@ -364,6 +571,7 @@ def source_info(data, box_size, n_pixels=5, sigma_threshold=1.5, device_out=Fals
     torch = _B.torch
     _check_image_shape(_shape_of(data))
     check_detect_args(_shape_of(data), n_pixels, 8)
+    check_deblend_args(_shape_of(data), _shape_of(data), n_pixels, nlevels, contrast)
     bkg = Background2D(data, box_size, filter_size=(3, 3), device_out=True)
     d, batched = _to_dev(data)
     bg = bkg.background if batched else bkg.background[None]
@@ -380,10 +588,14 @@ def source_info(data, box_size, n_pixels=5, sigma_threshold=1.5, device_out=Fals
     if not batched and n[0] == 0:
         warnings.warn("No sources were found.", NoDetectionsWarning)
         return None, bkg
+    seg = None
+    if deblend:
+        res = _deblend_dev(conv, lab, n, int(n_pixels), nlevels, contrast, "exponential", 8)
+        seg, (lab, n) = _deblended_image(res, batched, device_out), res[:2]
     cat = SourceCatalog.__new__(SourceCatalog)
     cat._fill(sub, conv, lab, n.astype(np.int32), batched, device_out)
     cat.background = None
-    cat.segment_img = SegmentationImage(_out(lab, batched, device_out), n, batched)
+    cat.segment_img = seg or SegmentationImage(_out(lab, batched, device_out), n, batched)
     cat.data, cat.convolved_data = _out(sub, batched, device_out), _out(conv, batched, device_out)
     return cat, bkg
 

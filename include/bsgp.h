@@ -403,9 +403,9 @@ int bsgp_solve_resume(bsgp_plan plan, int32_t B, const bsgp_params* params,
                       const void* state_dev, int32_t n_state, int64_t bytes_per_image,
                       const int32_t* index, const bsgp_outputs* out, void* stream);
 
-/* Source detection and segment measurement: the part of
- * utils.source_info (restoration/utils.py:240-247) that precedes deblending.
- * All three are asynchronous; images of a batch are processed on their own and
+/* Source detection, deblending and segment measurement: what
+ * utils.source_info (restoration/utils.py:235-247) does with photutils.
+ * All four are asynchronous; images of a batch are processed on their own and
  * get the bits they get alone; H * W < 2^31 and B <= 65535, else
  * BSGP_ERR_UNSUPPORTED.
  *
@@ -443,6 +443,54 @@ int bsgp_segment_catalog(const double* data, const double* conv, const int32_t* 
                          int32_t H, int32_t W, int32_t cap, const int32_t* nlabels,
                          int32_t* int_cols_out, double* f64_cols_out, int32_t* status_out,
                          void* stream);
+
+/* What SourceFinder(npixels, deblend=True) (utils.py:235, called at :242) adds to
+ * detect_sources: photutils' deblend_sources, modelled on its documentation and
+ * pinned to scipy.ndimage.label and skimage.segmentation.watershed.  Per
+ * parent segment of labels (pixel set M, v = data on M):
+ *  D1 smin, smax, ssum = sum v; smin == smax leaves the parent as it is.
+ *  D2 thresholds k = 1..nlevels: linear smin + (smax - smin) / (nlevels + 1) * k;
+ *     exponential m * (smax / m)^(k / (nlevels + 1)), m = smin, or 0.01 smax when
+ *     smin == 0; exponential with smin < 0 uses linear.
+ *  D3 per level, rising: the components of {p in M : v_p > t_k} with the given
+ *     connectivity, those of fewer than npixels pixels dropped.
+ *  D4 the regions start as {M}; a region holding two or more of a level's
+ *     components is replaced by them; {M} after the last level leaves the
+ *     parent.  The regions are the markers; a marker's identity is its first
+ *     pixel in raster order.
+ *  D5 watershed(-v, markers, mask=M): a priority queue keyed by (-v, index)
+ *     (ties: the smaller index first; skimage: insertion age) holds the marker
+ *     pixels; the smallest key is popped, and each unlabelled neighbour in M
+ *     takes the popped pixel's label and is entered.
+ *  D6 while a child has sum(v over it) / ssum < contrast, the child with the
+ *     smallest fraction (tie: the smaller marker identity) is cleared and the
+ *     flood repeated from the other children's full regions; fewer than two
+ *     children leave the parent.
+ *  D7 output labels 1..n: the parents left as they are first, in input order,
+ *     then the children by parent, in marker order.
+ * A pixel of M the flood cannot reach (connectivity 4 inside an 8-connected
+ * parent) becomes 0, as the watershed leaves it.
+ * data: float64 [B][H][W] (source_info passes the convolved image); labels:
+ * int32 [B][H][W]; cap, nlabels [B] and int_cols [B][cap][5] as
+ * bsgp_segment_catalog takes and writes them; select: bytes [B][cap], nonzero =
+ * deblend this label, or NULL for all.  A parent with area < 2 npixels cannot
+ * split and is skipped.  A parent whose bounding box holds more than
+ * BSGP_DEBLEND_MAX_BOX pixels is left as it is and sets BSGP_DEBLEND_OVER_CAP in
+ * status_out[b]; a label outside 0..min(cap, nlabels[b]) becomes 0 and sets
+ * BSGP_DEBLEND_BAD_LABEL.  labels_out (int32 [B][H][W], not labels itself),
+ * nlabels_out [B] and status_out [B] are written on the device.
+ * BSGP_ERR_ARG: nlevels < 1, contrast outside [0, 1], npixels < 1, connectivity
+ * not 4 or 8, an unknown mode. */
+#define BSGP_DEBLEND_MAX_BOX 4096
+#define BSGP_DEBLEND_LINEAR 0
+#define BSGP_DEBLEND_EXPONENTIAL 1
+#define BSGP_DEBLEND_OVER_CAP 1
+#define BSGP_DEBLEND_BAD_LABEL 2
+int bsgp_deblend_sources(const double* data, const int32_t* labels, int32_t B, int32_t H, int32_t W,
+                         int32_t cap, const int32_t* nlabels, const int32_t* int_cols,
+                         const uint8_t* select, int32_t npixels, int32_t nlevels, double contrast,
+                         int32_t mode, int32_t connectivity, int32_t* labels_out,
+                         int32_t* nlabels_out, int32_t* status_out, void* stream);
 
 /* Star-stamp metrics: what application_sgp_star_stamps.py:117-142
  * computes for the observed and the restored stamp.  All three are

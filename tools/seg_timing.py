@@ -12,8 +12,13 @@ script (profiles/seg/README.md).  Each stage is put beside a device-to-device
 copy that moves the bytes the stage must read and write once (inputs read,
 outputs written; a copy of n bytes reads n and writes n, so the copy is of half
 their sum), and the detection and measurement beside their scipy.ndimage
-composition on the host.  A last line times the measurement of an all-true
-2048x2048 image, whose one segment is scanned by a single wave.
+composition on the host.  The deblend stage (bsgp_deblend_sources on the
+detection's labels and the measurement's int_cols) is timed four ways: every
+parent, no parent selected (the fixed cost: numbering and relabel), only the
+parents that split and only those that do not; only a split parent runs the
+single-lane flood, so the last two bound its share.  A last line times the
+measurement of an all-true 2048x2048 image, whose one segment is scanned by a
+single wave.
 
     python tools/seg_timing.py --out profiles/seg/timing.json
 """
@@ -143,6 +148,32 @@ def run(name, shape, box, host_images, rng, npix=5, sigma_threshold=1.5):
     t_cat, _ = timed(measure)
     assert not cst.cpu().numpy().any()
 
+    # deblending: the convolved image, the detection's labels, the measurement's int_cols
+    lab2, nlab2, dst = torch.empty(shape, **i32), torch.empty((n,), **i32), torch.empty((n,), **i32)
+    sel = torch.zeros((n, cap), dtype=torch.uint8, device="cuda")
+
+    def deblend(select=None):
+        B.check(L.bsgp_deblend_sources(B._ptr(conv), B._ptr(lab), n, H, W, cap, B._ptr(nlab),
+                                       B._ptr(ic), B._ptr(select), npix, 32, 0.001,
+                                       B.BSGP_DEBLEND_EXPONENTIAL, 8, B._ptr(lab2), B._ptr(nlab2),
+                                       B._ptr(dst), s()))
+
+    t_deb, t_deb_all = timed(deblend)
+    counts2 = nlab2.cpu().numpy()
+    over = int((dst.cpu().numpy() & B.BSGP_DEBLEND_OVER_CAP != 0).sum())
+    # parent of every output label, hence the parents that split
+    par = torch.zeros((n, int(counts2.max()) + 1), **i32)
+    par.scatter_(1, lab2.reshape(n, -1).long(), lab.reshape(n, -1))
+    kids = torch.zeros((n, cap + 1), **i32)
+    live = torch.arange(par.shape[1], device="cuda")[None, :] <= nlab2[:, None]
+    kids.scatter_add_(1, par.long(), live.to(torch.int32))
+    split = (kids[:, 1:] > 1)
+    t_none, _ = timed(lambda: deblend(sel))
+    sel_split, sel_rest = split.to(torch.uint8).contiguous(), (~split).to(torch.uint8).contiguous()
+    t_split, _ = timed(lambda: deblend(sel_split))
+    t_rest, _ = timed(lambda: deblend(sel_rest))
+    can_split = int((ic[:, :, 0] >= 2 * npix).sum().item())
+
     def whole():
         background(), threshold_conv(), detect(), measure()
 
@@ -167,6 +198,11 @@ def run(name, shape, box, host_images, rng, npix=5, sigma_threshold=1.5):
         "ms_background": t_bkg, "ms_threshold_and_convolution": t_thr, "ms_convolution_alone": t_conv,
         "ms_detect_labelling_and_compaction": t_det, "ms_detect_all": t_det_all,
         "ms_measure": t_cat, "ms_all_stages_one_after_another": t_all, "ms_all_stages_all": t_all_all,
+        "ms_deblend": t_deb, "ms_deblend_all": t_deb_all,
+        "ms_deblend_no_parent_selected": t_none, "ms_deblend_only_parents_that_split": t_split,
+        "ms_deblend_only_parents_that_do_not_split": t_rest,
+        "deblend_parents_of_at_least_2_npixels": can_split, "deblend_parents_split": int(split.sum().item()),
+        "deblend_labels_out_total": int(counts2.sum()), "deblend_images_with_a_parent_over_the_box_cap": over,
         "stage_bytes_read_plus_written": stage_bytes,
         "ms_d2d_copy_of_half_those_bytes": copies,
         "host_scipy_detect_and_measure_s": host_s, "host_images": host_images,
