@@ -1680,11 +1680,13 @@ int bsgp_segment_catalog(const double* data, const double* conv, const int32_t* 
   return BSGP_OK;
 }
 
-int bsgp_deblend_sources(const double* data, const int32_t* labels, int32_t B, int32_t H, int32_t W,
-                         int32_t cap, const int32_t* nlabels, const int32_t* int_cols,
-                         const uint8_t* select, int32_t npixels, int32_t nlevels, double contrast,
-                         int32_t mode, int32_t connectivity, int32_t* labels_out,
-                         int32_t* nlabels_out, int32_t* status_out, void* stream) {
+// both deblending entry points; lds_max_box < 0: bsgp_deblend_sources (no global-memory path)
+static int deblend_sources(const double* data, const int32_t* labels, int32_t B, int32_t H, int32_t W,
+                           int32_t cap, const int32_t* nlabels, const int32_t* int_cols,
+                           const uint8_t* select, int32_t npixels, int32_t nlevels, double contrast,
+                           int32_t mode, int32_t connectivity, int32_t lds_max_box,
+                           int32_t* labels_out, int32_t* nlabels_out, int32_t* status_out,
+                           void* stream) {
   if (!data) return fail(BSGP_ERR_ARG, "data is NULL");
   if (!labels || !nlabels || !int_cols) return fail(BSGP_ERR_ARG, "labels / nlabels / int_cols is NULL");
   if (!labels_out || !nlabels_out || !status_out)
@@ -1704,12 +1706,20 @@ int bsgp_deblend_sources(const double* data, const int32_t* labels, int32_t B, i
   a.B = B, a.H = H, a.W = W, a.cap = cap, a.npixels = npixels, a.nlevels = nlevels;
   a.conn = connectivity, a.mode = mode, a.contrast = contrast;
   a.labels_out = labels_out, a.nlabels_out = nlabels_out, a.status = status_out;
+  a.large = lds_max_box >= 0;
+  a.lds_max_box = a.large ? lds_max_box : kDeblendMaxBox;
   hipStream_t s = (hipStream_t)stream;
-  // stream-ordered workspace: the call stays asynchronous
-  const size_t rows = (size_t)B * cap;
+  // stream-ordered workspace: the call stays asynchronous.  The global-memory
+  // path adds 32 bytes per pixel (one double and six ints), sized by B, H, W
+  // alone and never initialised.
+  const size_t rows = (size_t)B * cap, px = a.large ? (size_t)B * H * W : 0;
   void* w = nullptr;
-  HIP_TRY(hipMallocAsync(&w, 2 * rows * sizeof(int), s));
-  a.nchild = static_cast<int*>(w);
+  HIP_TRY(hipMallocAsync(&w, px * (sizeof(double) + 6 * sizeof(int)) + 2 * rows * sizeof(int), s));
+  a.hkey = static_cast<double*>(w);
+  a.lev = reinterpret_cast<int*>(a.hkey + px);
+  a.reg = a.lev + px, a.cnt = a.reg + px, a.kept = a.cnt + px, a.mk = a.kept + px;
+  a.hidx = a.mk + px;
+  a.nchild = a.hidx + px;
   a.base = a.nchild + rows;
   hipError_t e = hipMemsetAsync(a.nchild, 0, rows * sizeof(int), s);
   if (e == hipSuccess) e = hipMemsetAsync(status_out, 0, (size_t)B * sizeof(int), s);
@@ -1718,6 +1728,29 @@ int bsgp_deblend_sources(const double* data, const int32_t* labels, int32_t B, i
   if (e != hipSuccess) return fail(BSGP_ERR_HIP, std::string("deblend launch: ") + hipGetErrorString(e));
   HIP_TRY(ef);
   return BSGP_OK;
+}
+
+int bsgp_deblend_sources(const double* data, const int32_t* labels, int32_t B, int32_t H, int32_t W,
+                         int32_t cap, const int32_t* nlabels, const int32_t* int_cols,
+                         const uint8_t* select, int32_t npixels, int32_t nlevels, double contrast,
+                         int32_t mode, int32_t connectivity, int32_t* labels_out,
+                         int32_t* nlabels_out, int32_t* status_out, void* stream) {
+  return deblend_sources(data, labels, B, H, W, cap, nlabels, int_cols, select, npixels, nlevels,
+                         contrast, mode, connectivity, -1, labels_out, nlabels_out, status_out,
+                         stream);
+}
+
+int bsgp_deblend_sources_large(const double* data, const int32_t* labels, int32_t B, int32_t H,
+                               int32_t W, int32_t cap, const int32_t* nlabels,
+                               const int32_t* int_cols, const uint8_t* select, int32_t npixels,
+                               int32_t nlevels, double contrast, int32_t mode,
+                               int32_t connectivity, int32_t lds_max_box, int32_t* labels_out,
+                               int32_t* nlabels_out, int32_t* status_out, void* stream) {
+  if (lds_max_box < 0 || lds_max_box > BSGP_DEBLEND_MAX_BOX)
+    return fail(BSGP_ERR_ARG, "lds_max_box must lie in 0 .. BSGP_DEBLEND_MAX_BOX");
+  return deblend_sources(data, labels, B, H, W, cap, nlabels, int_cols, select, npixels, nlevels,
+                         contrast, mode, connectivity, lds_max_box, labels_out, nlabels_out,
+                         status_out, stream);
 }
 
 int bsgp_radial_profile(const void* data, int32_t dtype, int32_t B, int32_t H, int32_t W,

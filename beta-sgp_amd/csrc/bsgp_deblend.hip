@@ -15,6 +15,13 @@
 //                    child summing in a fixed order.  Writes the parent's child
 //                    count and, for a split parent, every pixel's child rank
 //                    into labels_out.
+//  k_deblend_large   the same for a parent whose box is over the LDS cap
+//                    (bsgp_deblend_sources_large): one workgroup per parent,
+//                    the working set in global memory keyed by image pixel,
+//                    the heap's first levels in LDS with the key in the entry,
+//                    the frontier collected and heapified by all threads, the
+//                    flood itself on one lane.  Same identities, orders and
+//                    sums: a parent gets the same labels from either kernel.
 //  k_deblend_number  one workgroup per image: D7's numbering from the child
 //                    counts (two scans in label order).
 //  k_deblend_relabel one thread per pixel: the final int32 label image.
@@ -211,8 +218,8 @@ __global__ void __launch_bounds__(256) k_deblend_parent(DeblendArgs a) {
   if (area <= 0 || area < 2 * (long long)a.npixels || (a.sel && !a.sel[row])) return;
   const int x0 = ic[1], y0 = ic[3], bw = ic[2] - x0 + 1, bh = ic[4] - y0 + 1;
   if (x0 < 0 || y0 < 0 || bw < 1 || bh < 1 || ic[2] >= a.W || ic[4] >= a.H) return;
-  if ((long long)bw * bh > kBox) {
-    if (tid == 0) atomicOr(a.status + b, BSGP_DEBLEND_OVER_CAP);
+  if ((long long)bw * bh > a.lds_max_box) {  // at most kBox; k_deblend_large's when there is one
+    if (!a.large && tid == 0) atomicOr(a.status + b, BSGP_DEBLEND_OVER_CAP);
     return;
   }
   const int n = bw * bh, want = i + 1;
@@ -406,6 +413,441 @@ __global__ void __launch_bounds__(256) k_deblend_parent(DeblendArgs a) {
   if (tid == 0) a.nchild[row] = alive;
 }
 
+// ---- parents over the LDS cap: the same steps with the working set in global
+// memory, keyed by image pixel (DeblendArgs).  Boxes of parents overlap, their
+// pixel sets do not: a parent writes its own pixels' entries before it reads
+// them and reads a neighbour's only after labels[q] == want, so the arrays are
+// shared by all parents of a call and never initialised.  Identities are pixel
+// indices of the image, whose order inside a box is the box's raster order;
+// every float sum runs over box indices k with stride 64, as in k_deblend_parent.
+namespace {
+
+constexpr int kHeapLds = 5120;               // heap entries in LDS: the heap's first levels
+constexpr int kAccSlots = kHeapLds / 64 / 4;  // D6: children one wave sums in one pass over the box
+
+// the arrays integer atomics write are read at the scope of those atomics
+__device__ __forceinline__ int gl_load(const int* p) {
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ void gl_store(int* p, int v) {
+  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// seg_find / seg_unite of bsgp_segment.hip
+__device__ __forceinline__ int gl_find(int* L, int a) {
+  int p = gl_load(L + a);
+  while (p != a) {
+    const int g = gl_load(L + p);
+    if (g != p) atomicMin(L + a, g);
+    a = p;
+    p = g;
+  }
+  return a;
+}
+
+__device__ __forceinline__ void gl_unite(int* L, int a, int b) {
+  for (;;) {
+    a = gl_find(L, a);
+    b = gl_find(L, b);
+    if (a == b) return;
+    if (a < b) {
+      const int t = a;
+      a = b;
+      b = t;
+    }
+    const int old = atomicMin(L + a, b);
+    if (old == a) return;
+    a = old;
+  }
+}
+
+// The flood's heap: entries (value, pixel) in db_before's order, the key inside
+// the entry.  Entry i < kHeapLds lives in LDS, the others in the parent's slice
+// of the global arrays (at most `area` entries: a pixel enters at most once).
+struct LHeap {
+  double* lk;
+  int* li;
+  double* gk;
+  int* gi;
+  __device__ __forceinline__ void get(int i, double& v, int& p) const {
+    if (i < kHeapLds) v = lk[i], p = li[i];
+    else v = gk[i], p = gi[i];
+  }
+  __device__ __forceinline__ void set(int i, double v, int p) const {
+    if (i < kHeapLds) lk[i] = v, li[i] = p;
+    else gk[i] = v, gi[i] = p;
+  }
+};
+
+__device__ __forceinline__ bool lh_before(double x, int a, double y, int b) {
+  return x > y || (x == y && a < b);
+}
+
+// entry (v, p) sinks from the hole at i
+__device__ __forceinline__ void lh_sift_down(const LHeap& h, int n, int i, double v, int p) {
+  for (;;) {
+    int c = 2 * i + 1;
+    if (c >= n) break;
+    double cv;
+    int cp;
+    h.get(c, cv, cp);
+    if (c + 1 < n) {
+      double v2;
+      int p2;
+      h.get(c + 1, v2, p2);
+      if (lh_before(v2, p2, cv, cp)) ++c, cv = v2, cp = p2;
+    }
+    if (!lh_before(cv, cp, v, p)) break;
+    h.set(i, cv, cp);
+    i = c;
+  }
+  h.set(i, v, p);
+}
+
+__device__ __forceinline__ void lh_push(const LHeap& h, int& n, double v, int p) {
+  int i = n++;
+  while (i > 0) {
+    const int up = (i - 1) >> 1;
+    double uv;
+    int uq;
+    h.get(up, uv, uq);
+    if (!lh_before(v, p, uv, uq)) break;
+    h.set(i, uv, uq);
+    i = up;
+  }
+  h.set(i, v, p);
+}
+
+// image pixel of box pixel k
+struct LBox {
+  int x0, y0, bw, W;
+  __device__ __forceinline__ int pix(int k) const {
+    const int r = k / bw;
+    return (y0 + r) * W + x0 + (k - r * bw);
+  }
+};
+
+}  // namespace
+
+__global__ void __launch_bounds__(256) k_deblend_large(DeblendArgs a) {
+  __shared__ double lk[kHeapLds];  // D5: heap keys; D6: lane partials [wave][slot][lane]
+  __shared__ int li[kHeapLds];     // D5: heap pixels
+  __shared__ double thr[256];
+  __shared__ double sred[8];
+  __shared__ int sint[12];
+  __shared__ unsigned long long soff;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int i = blockIdx.x, b = blockIdx.y;
+  if (i >= db_rows(a, b)) return;
+  const size_t row = (size_t)b * a.cap + i;
+  const int* ic = a.icols + row * 5;
+  const int area = ic[0];
+  if (area <= 0 || area < 2 * (long long)a.npixels || (a.sel && !a.sel[row])) return;
+  const int x0 = ic[1], y0 = ic[3], bw = ic[2] - x0 + 1, bh = ic[4] - y0 + 1;
+  if (x0 < 0 || y0 < 0 || bw < 1 || bh < 1 || ic[2] >= a.W || ic[4] >= a.H) return;
+  if ((long long)bw * bh <= a.lds_max_box) return;  // k_deblend_parent's
+  if (area > kDeblendLargeMaxArea) {
+    if (tid == 0) atomicOr(a.status + b, BSGP_DEBLEND_OVER_CAP);
+    return;
+  }
+  const int n = bw * bh, want = i + 1, hw = a.H * a.W;  // the box lies in the image: n <= hw < 2^31
+  const size_t o = (size_t)b * hw;
+  const LBox bx{x0, y0, bw, a.W};
+  const int* labs = a.labels + o;
+  const double* dat = a.data + o;
+  int *lev = a.lev + o, *reg = a.reg + o, *cnt = a.cnt + o, *kept = a.kept + o;
+  int* fl = a.labels_out + o;  // D5: flood labels; then the child ranks
+
+  // the parent's slice of the marker and heap arrays starts at the sum of the
+  // image's lower areas; the root; the pixel count that slice relies on
+  if (tid == 0) sint[0] = hw, sint[1] = 0, sint[5] = 0, sint[6] = 0, soff = 0ull;
+  __syncthreads();
+  {
+    unsigned long long part = 0ull;
+    for (int j = tid; j < i; j += 256) {
+      const int ar = a.icols[((size_t)b * a.cap + j) * 5];
+      part += ar > 0 ? (unsigned long long)(ar < hw ? ar : hw) : 0ull;
+    }
+    if (part) atomicAdd(&soff, part);
+    int own = 0, mn = hw;
+    for (int k = tid; k < n; k += 256) {
+      const int q = bx.pix(k);
+      if (labs[q] != want) continue;
+      ++own;
+      mn = q < mn ? q : mn;
+    }
+    if (own) atomicAdd(&sint[6], own), atomicMin(&sint[0], mn);
+  }
+  __syncthreads();
+  const int root0 = sint[0];
+  // int_cols that do not describe labels: the slice is not the parent's
+  if (sint[6] != area || soff + (unsigned long long)area > (unsigned long long)hw) return;
+  const size_t off = o + (size_t)soff;
+  int* mk = a.mk + off;
+  const LHeap heap{lk, li, a.hkey + off, a.hidx + off};
+  for (int k = tid; k < n; k += 256) {
+    const int q = bx.pix(k);
+    if (labs[q] == want) reg[q] = root0;
+  }
+
+  // D1
+  if (wave == 0) {
+    double s = 0.0, mn = db_inf(), mx = -db_inf();
+    for (int k = lane; k < n; k += 64) {
+      const int q = bx.pix(k);
+      if (labs[q] != want) continue;
+      const double x = dat[q];
+      s += x;
+      mn = x < mn ? x : mn;
+      mx = x > mx ? x : mx;
+    }
+    s = wave_sum(s);
+    mn = wave_min(mn);
+    mx = wave_max(mx);
+    if (lane == 0) sred[0] = mn, sred[1] = mx, sred[2] = s;
+  }
+  __syncthreads();
+  const double smin = sred[0], smax = sred[1], ssum = sred[2];
+  if (!(smin < smax)) return;
+
+  // D2 to D4
+  const bool linear = a.mode == BSGP_DEBLEND_LINEAR || smin < 0.0;
+  const double m = smin != 0.0 ? smin : 0.01 * smax;
+  const double den = (double)(a.nlevels + 1);
+  for (int lv = 1; lv <= a.nlevels; ++lv) {
+    if (((lv - 1) & 255) == 0) {
+      const double k = (double)(lv + tid);
+      thr[tid] = linear ? smin + (smax - smin) / den * k : m * pow(smax / m, k / den);
+      __syncthreads();
+    }
+    const double t = thr[(lv - 1) & 255];
+    int above = 0;
+    for (int k = tid; k < n; k += 256) {
+      const int q = bx.pix(k);
+      if (labs[q] != want) continue;
+      const bool on = dat[q] > t;
+      gl_store(lev + q, on ? q : -1);
+      gl_store(cnt + q, 0);
+      gl_store(kept + q, 0);
+      above += on;
+    }
+    if (above) atomicAdd(&sint[5], above);
+    __syncthreads();
+    if (sint[5] < 2 * (long long)a.npixels) break;
+    for (int k = tid; k < n; k += 256) {
+      const int y = k / bw, x = k - y * bw, p = (y0 + y) * a.W + x0 + x, q = p - a.W;
+      if (labs[p] != want || gl_load(lev + p) < 0) continue;
+      const bool w = x > 0 && labs[p - 1] == want && gl_load(lev + p - 1) >= 0;
+      const bool nn = y > 0 && labs[q] == want && gl_load(lev + q) >= 0;
+      if (a.conn == 4) {
+        if (w) gl_unite(lev, p, p - 1);
+        if (nn) gl_unite(lev, p, q);
+        continue;
+      }
+      if (nn) {
+        gl_unite(lev, p, q);
+        continue;
+      }
+      const bool nw = y > 0 && x > 0 && labs[q - 1] == want && gl_load(lev + q - 1) >= 0;
+      const bool ne = y > 0 && x < bw - 1 && labs[q + 1] == want && gl_load(lev + q + 1) >= 0;
+      if (ne) gl_unite(lev, p, q + 1);
+      if (nw) gl_unite(lev, p, q - 1);
+      else if (w) gl_unite(lev, p, p - 1);
+    }
+    __syncthreads();
+    for (int k = tid; k < n; k += 256) {
+      const int p = bx.pix(k);
+      if (labs[p] != want || gl_load(lev + p) < 0) continue;
+      const int r = gl_find(lev, p);
+      if (r != p) gl_store(lev + p, r);
+      atomicAdd(cnt + r, 1);
+    }
+    if (tid == 0) sint[5] = 0;  // every thread read it before the barrier above
+    __syncthreads();
+    for (int k = tid; k < n; k += 256) {
+      const int p = bx.pix(k);
+      if (labs[p] != want) continue;
+      if (gl_load(lev + p) == p && gl_load(cnt + p) >= a.npixels && reg[p] >= 0)
+        atomicAdd(kept + reg[p], 1);
+    }
+    __syncthreads();
+    for (int k = tid; k < n; k += 256) {
+      const int p = bx.pix(k);
+      if (labs[p] != want) continue;
+      const int R = reg[p];
+      if (R < 0 || gl_load(kept + R) < 2) continue;
+      const int l = gl_load(lev + p);
+      reg[p] = (l >= 0 && gl_load(cnt + l) >= a.npixels) ? l : kFree;
+      sint[1] = 1;
+    }
+    __syncthreads();
+  }
+  if (!sint[1]) return;
+
+  // the markers, in raster order; kept[c] = the list index of marker c
+  for (int k = tid; k < n; k += 256) {
+    const int p = bx.pix(k);
+    if (labs[p] == want) fl[p] = reg[p];
+  }
+  if (wave == 0) {
+    int nm = 0;
+    for (int base = 0; base < n; base += 64) {
+      const int k = base + lane, p = k < n ? bx.pix(k) : 0;
+      const bool f = k < n && labs[p] == want && reg[p] == p;
+      const unsigned long long bal = __ballot(f);
+      if (f) {
+        const int ci = nm + __popcll(bal & ((1ull << lane) - 1ull));
+        mk[ci] = p;
+        gl_store(kept + p, ci);
+      }
+      nm += __popcll(bal);
+    }
+    if (lane == 0) sint[2] = nm;
+  }
+  __syncthreads();
+  const int nm = sint[2];
+  int alive = nm;
+
+  // D5, D6
+  for (;;) {
+    // the frontier, labelled pixels with a free neighbour, by all threads; the
+    // heap's order is total and strict, so the pops do not depend on the order
+    // the entries arrive in
+    if (tid == 0) sint[8] = 0;
+    __syncthreads();
+    for (int k = tid; k < n; k += 256) {
+      const int y = k / bw + y0, x = k - (k / bw) * bw + x0, p = y * a.W + x;
+      if (labs[p] != want || fl[p] < 0) continue;
+      bool open = false;
+      for (int j = 0; j < 8; ++j) {
+        const int jj = j < 4 ? j : j + 1;
+        const int dy = jj / 3 - 1, dx = jj - (jj / 3) * 3 - 1;
+        if (a.conn == 4 && dx != 0 && dy != 0) continue;
+        const int xx = x + dx, yy = y + dy;
+        if (xx < 0 || xx >= a.W || yy < 0 || yy >= a.H) continue;
+        const int q = p + dy * a.W + dx;
+        if (labs[q] == want && fl[q] == kFree) open = true;
+      }
+      if (open) heap.set(atomicAdd(&sint[8], 1), dat[p], p);
+    }
+    __syncthreads();
+    int hn = sint[8];
+    // heapify: the nodes of one depth sink at once, their subtrees are disjoint
+    for (int d = 30 - __clz(hn | 1); d >= 0; --d) {
+      const int lo = (1 << d) - 1, hi = 2 * lo + 1 < hn ? 2 * lo + 1 : hn;
+      for (int j = lo + tid; j < hi; j += 256) {
+        double v;
+        int p;
+        heap.get(j, v, p);
+        lh_sift_down(heap, hn, j, v, p);
+      }
+      __syncthreads();
+    }
+    if (tid == 0) {
+      while (hn > 0) {
+        double v, lv;
+        int p, lp;
+        heap.get(0, v, p);
+        heap.get(--hn, lv, lp);
+        if (hn > 0) lh_sift_down(heap, hn, 0, lv, lp);
+        const int y = p / a.W, x = p - y * a.W, l = fl[p];
+        // the eight neighbours' label, flood label and value in one batch of
+        // independent loads (the lane waits once, not per neighbour); a
+        // neighbour outside the image reads p itself, which is labelled
+        int nq[8], nl[8], nf[8];
+        double nv[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const int jj = j < 4 ? j : j + 1;
+          const int dy = jj / 3 - 1, dx = jj - (jj / 3) * 3 - 1;
+          const int xx = x + dx, yy = y + dy;
+          const bool ok = !(a.conn == 4 && dx != 0 && dy != 0) && xx >= 0 && xx < a.W && yy >= 0 &&
+                          yy < a.H;
+          nq[j] = ok ? p + dy * a.W + dx : p;
+          nl[j] = labs[nq[j]];
+          nf[j] = fl[nq[j]];
+          nv[j] = dat[nq[j]];
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          if (nl[j] == want && nf[j] == kFree) {
+            fl[nq[j]] = l;
+            lh_push(heap, hn, nv[j], nq[j]);
+          }
+        }
+      }
+      sint[3] = 0;
+    }
+    __syncthreads();
+    // every child's fraction: a wave takes kAccSlots children per pass over the
+    // box, lane partials in box raster order with stride 64 (db_wave_sum_of's sums)
+    double bf = db_inf();
+    int bc = 0x7fffffff, below = 0;
+    double* acc = lk + wave * (kAccSlots * 64);
+    for (int base = wave * kAccSlots; base < nm; base += 4 * kAccSlots) {
+      const int ng = nm - base < kAccSlots ? nm - base : kAccSlots;
+      for (int s = 0; s < ng; ++s) acc[s * 64 + lane] = 0.0;
+      for (int k = lane; k < n; k += 64) {
+        const int p = bx.pix(k);
+        if (labs[p] != want) continue;
+        const int l = fl[p];
+        if (l < 0) continue;
+        const int s = gl_load(kept + l) - base;
+        if (s >= 0 && s < ng) acc[s * 64 + lane] += dat[p];
+      }
+      for (int s = 0; s < ng; ++s) {
+        const int c = mk[base + s];
+        if (c < 0) continue;
+        const double frac = wave_sum(acc[s * 64 + lane]) / ssum;
+        if (frac < a.contrast) below = 1;
+        if (frac < bf || (frac == bf && c < bc)) bf = frac, bc = c;
+      }
+    }
+    if (lane == 0) {
+      sred[4 + wave] = bf, sint[4 + wave] = bc;
+      if (below) atomicOr(&sint[3], 1);
+    }
+    __syncthreads();
+    if (!sint[3]) break;
+    bf = sred[4], bc = sint[4];
+    for (int k = 1; k < 4; ++k) {
+      const double f = sred[4 + k];
+      const int c = sint[4 + k];
+      if (f < bf || (f == bf && c < bc)) bf = f, bc = c;
+    }
+    for (int k = tid; k < n; k += 256) {
+      const int p = bx.pix(k);
+      if (labs[p] == want && fl[p] == bc) fl[p] = kFree;
+    }
+    for (int ci = tid; ci < nm; ci += 256)
+      if (mk[ci] == bc) mk[ci] = -1;
+    --alive;
+    __syncthreads();
+    if (alive < 2) break;  // one child or none: the parent stays
+  }
+  if (alive < 2) return;
+
+  // child ranks in marker order (kept[c]), into labels_out
+  if (wave == 0) {
+    int r = 0;
+    for (int base = 0; base < nm; base += 64) {
+      const int ci = base + lane;
+      const int c = ci < nm ? mk[ci] : -1;
+      const unsigned long long bal = __ballot(c >= 0);
+      if (c >= 0) gl_store(kept + c, r + __popcll(bal & ((1ull << lane) - 1ull)));
+      r += __popcll(bal);
+    }
+  }
+  __syncthreads();
+  for (int k = tid; k < n; k += 256) {
+    const int p = bx.pix(k);
+    if (labs[p] != want) continue;
+    const int l = fl[p];
+    fl[p] = l >= 0 ? gl_load(kept + l) : -1;
+  }
+  if (tid == 0) a.nchild[row] = alive;
+}
+
 // D7: parents left as they are first, in label order, then the children by parent
 __global__ void __launch_bounds__(256) k_deblend_number(DeblendArgs a) {
   __shared__ int wsum[4];
@@ -455,6 +897,7 @@ hipError_t launch_deblend(const DeblendArgs& a, hipStream_t s) {
   const int hw = a.H * a.W;
   const dim3 block(256);
   hipLaunchKernelGGL(k_deblend_parent, dim3(a.cap, a.B), block, 0, s, a);
+  if (a.large) hipLaunchKernelGGL(k_deblend_large, dim3(a.cap, a.B), block, 0, s, a);
   hipLaunchKernelGGL(k_deblend_number, dim3(a.B), block, 0, s, a);
   hipLaunchKernelGGL(k_deblend_relabel, dim3((unsigned)(((size_t)hw + 255) / 256), a.B), block, 0,
                      s, a);

@@ -209,7 +209,19 @@ struct DeblendArgs {
   int* labels_out;   // [B][H][W]: child ranks of split parents, then the final labels
   int* nlabels_out;  // [B]
   int* status;       // [B]: BSGP_DEBLEND_* bits (zeroed first)
+  // k_deblend_large (large != 0): parents whose box holds more than lds_max_box
+  // pixels.  Workspace per image pixel, never initialised: a parent writes its
+  // own pixels' entries before it reads them.
+  int lds_max_box, large;
+  int* lev;      // [B][H*W]: the level's union-find parents (-1: not above the level)
+  int* reg;      // [B][H*W]: the region (its root) a pixel is in, or kFree
+  int* cnt;      // [B][H*W]: a root's component area
+  int* kept;     // [B][H*W]: kept roots per region; then a marker's list index, then its rank
+  int* mk;       // [B][H*W]: marker lists, a parent's at the sum of the image's lower areas
+  int* hidx;     // [B][H*W]: heap entries beyond the LDS part, pixel indices, at the same offset
+  double* hkey;  // [B][H*W]: their keys
 };
+constexpr int kDeblendLargeMaxArea = BSGP_DEBLEND_LARGE_MAX_AREA;
 hipError_t launch_deblend(const DeblendArgs& a, hipStream_t s);
 // ---- star-stamp metrics (bsgp_stamps.hip) ----------------------
 constexpr int kStampMaxPixels = 16384;  // H * W of one stamp

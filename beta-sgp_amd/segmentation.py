@@ -52,11 +52,13 @@ class NoDetectionsWarning(UserWarning):
 
 
 class DeblendBoxWarning(UserWarning):
-    """A parent segment's bounding box holds more than DEBLEND_MAX_BOX pixels:
-    it is left undeblended."""
+    """A parent segment's bounding box holds more than DEBLEND_MAX_BOX pixels
+    (with ``large_parents=True``: the segment holds more than
+    DEBLEND_LARGE_MAX_AREA pixels): it is left undeblended."""
 
 
 DEBLEND_MAX_BOX = _B.BSGP_DEBLEND_MAX_BOX
+DEBLEND_LARGE_MAX_AREA = _B.BSGP_DEBLEND_LARGE_MAX_AREA
 DEBLEND_MODES = {"linear": _B.BSGP_DEBLEND_LINEAR, "exponential": _B.BSGP_DEBLEND_EXPONENTIAL}
 
 
@@ -248,7 +250,7 @@ def _detect_dev(d, threshold, npixels, connectivity, mask):
 
 
 def check_deblend_args(shape, seg_shape, npixels, nlevels=32, contrast=0.001, mode="exponential",
-                       connectivity=8, relabel=True):
+                       connectivity=8, relabel=True, large_parents=False, lds_max_box=None):
     """The argument checks of deblend_sources (host only)."""
     _check_image_shape(shape)
     if tuple(seg_shape) != tuple(shape):
@@ -268,6 +270,16 @@ def check_deblend_args(shape, seg_shape, npixels, nlevels=32, contrast=0.001, mo
         raise ValueError(f"connectivity must be 4 or 8, got {connectivity!r}")
     if not relabel:
         raise ValueError("relabel=False is not offered: the output labels are consecutive")
+    if not isinstance(large_parents, (bool, np.bool_)):
+        raise ValueError(f"large_parents must be a bool, got {large_parents!r}")
+    if lds_max_box is None:
+        return
+    if isinstance(lds_max_box, (bool, np.bool_)) or int(lds_max_box) != lds_max_box \
+            or not 0 <= lds_max_box <= DEBLEND_MAX_BOX:
+        raise ValueError(f"lds_max_box must be an int in 0..{DEBLEND_MAX_BOX}, got {lds_max_box!r}")
+    if not large_parents and lds_max_box != DEBLEND_MAX_BOX:
+        raise ValueError("lds_max_box needs large_parents=True: without the global-memory path "
+                         f"the LDS cap is {DEBLEND_MAX_BOX}")
 
 
 def deblend_numbering(nchild, present=None):
@@ -286,11 +298,13 @@ def deblend_numbering(nchild, present=None):
     return base, int(kept.sum() + kids.sum())
 
 
-def _deblend_dev(d, lab, n, npixels, nlevels, contrast, mode, connectivity, select=None):
+def _deblend_dev(d, lab, n, npixels, nlevels, contrast, mode, connectivity, select=None,
+                 large_parents=False, lds_max_box=DEBLEND_MAX_BOX):
     """(int32 CUDA labels [B, H, W], host nlabels [B], host status [B], int32
     CUDA parents [B, max nlabels + 1]) of the deblended image; one wait for the
     kernels.  d: float64 CUDA [B, H, W]; lab: int32 CUDA; n: host
-    int32 [B]; select: host bool [B, cap] or None."""
+    int32 [B]; select: host bool [B, cap] or None.  large_parents:
+    bsgp_deblend_sources_large with lds_max_box, else bsgp_deblend_sources."""
     torch = _B.torch
     B, H, W = d.shape
     n = np.ascontiguousarray(n, dtype=np.int32)
@@ -308,15 +322,21 @@ def _deblend_dev(d, lab, n, npixels, nlevels, contrast, mode, connectivity, sele
     out = torch.empty((B, H, W), dtype=torch.int32, device="cuda")
     nout = torch.empty((B,), dtype=torch.int32, device="cuda")
     dst = torch.empty((B,), dtype=torch.int32, device="cuda")
-    _B.check(_B.lib().bsgp_deblend_sources(_B._ptr(d), _B._ptr(lab), B, H, W, cap, _B._ptr(nd),
-                                           _B._ptr(ic), _B._ptr(sel), int(npixels), int(nlevels),
-                                           float(contrast), DEBLEND_MODES[mode], int(connectivity),
-                                           _B._ptr(out), _B._ptr(nout), _B._ptr(dst),
-                                           _B.current_stream()))
+    head = (_B._ptr(d), _B._ptr(lab), B, H, W, cap, _B._ptr(nd), _B._ptr(ic), _B._ptr(sel),
+            int(npixels), int(nlevels), float(contrast), DEBLEND_MODES[mode], int(connectivity))
+    tail = (_B._ptr(out), _B._ptr(nout), _B._ptr(dst), _B.current_stream())
+    if large_parents:
+        _B.check(_B.lib().bsgp_deblend_sources_large(*head, int(lds_max_box), *tail))
+    else:
+        _B.check(_B.lib().bsgp_deblend_sources(*head, *tail))
     # the count for the warning, by the kernel's own rule; which images hold such a parent is
     # the kernel's status bit, and the two must agree
     box = (ic[..., 2] - ic[..., 1] + 1).long() * (ic[..., 4] - ic[..., 3] + 1).long()
-    over = (ic[..., 0] >= 2 * int(npixels)) & (box > DEBLEND_MAX_BOX)
+    if large_parents:  # the area rule of the global-memory path
+        over = (box > int(lds_max_box)) & (ic[..., 0] > DEBLEND_LARGE_MAX_AREA)
+    else:
+        over = box > DEBLEND_MAX_BOX
+    over &= ic[..., 0] >= 2 * int(npixels)
     over &= torch.arange(cap, device="cuda")[None, :] < nd[:, None]
     if sel is not None:
         over &= sel != 0
@@ -328,12 +348,14 @@ def _deblend_dev(d, lab, n, npixels, nlevels, contrast, mode, connectivity, sele
                            "the segmentation image")
     flagged = (status & _B.BSGP_DEBLEND_OVER_CAP) != 0
     if not np.array_equal(flagged, nover > 0):
-        raise _B.BsgpError(_B.BSGP_ERR_HIP, "bsgp_deblend_sources reports parents over the box cap "
+        raise _B.BsgpError(_B.BSGP_ERR_HIP, "bsgp_deblend_sources reports parents over the cap "
                            f"in images {np.flatnonzero(flagged).tolist()}, int_cols hold them in "
                            f"images {np.flatnonzero(nover > 0).tolist()}")
     if flagged.any():
-        warnings.warn(f"{int(nover[flagged].sum())} parent segment(s) with a bounding box of more "
-                      f"than {DEBLEND_MAX_BOX} pixels were left undeblended", DeblendBoxWarning)
+        what = (f"of more than {DEBLEND_LARGE_MAX_AREA} pixels (the area limit of large_parents)"
+                if large_parents else f"with a bounding box of more than {DEBLEND_MAX_BOX} pixels")
+        warnings.warn(f"{int(nover[flagged].sum())} parent segment(s) {what} were left "
+                      "undeblended", DeblendBoxWarning)
     # parent of every output label: every pixel of a label writes the same input label
     par = torch.zeros((B, int(nout_h.max()) + 1), dtype=torch.int32, device="cuda")
     par.scatter_(1, out.reshape(B, -1).long(), lab.reshape(B, -1))
@@ -364,7 +386,8 @@ def _labels_dev(segment_img, batched):
 
 
 def deblend_sources(data, segment_img, npixels, labels=None, nlevels=32, contrast=0.001,
-                    mode="exponential", connectivity=8, relabel=True, device_out=False):
+                    mode="exponential", connectivity=8, relabel=True, device_out=False,
+                    large_parents=False, lds_max_box=DEBLEND_MAX_BOX):
     """photutils' ``deblend_sources`` for an image or a batch: every segment of
     ``segment_img`` (a :class:`SegmentationImage` or an integer label image) is
     split by multi-thresholding (``nlevels`` levels between its minimum and
@@ -378,11 +401,18 @@ def deblend_sources(data, segment_img, npixels, labels=None, nlevels=32, contras
     then the children by parent -- that also carries ``parent`` and ``status``
     (CUDA tensors with ``device_out=True``).  A segment
     whose bounding box holds more than ``DEBLEND_MAX_BOX`` pixels is left as it
-    is, with one :class:`DeblendBoxWarning` per call.  ``mode='sinh'`` and
-    ``relabel=False`` raise ``ValueError``."""
+    is, with one :class:`DeblendBoxWarning` per call.  With
+    ``large_parents=True`` (``bsgp_deblend_sources_large``) such a segment is
+    deblended too, by the kernel that works in global memory, and gets the
+    labels the LDS kernel would give it; only a segment of more than
+    ``DEBLEND_LARGE_MAX_AREA`` pixels is left, flagged and warned about.
+    ``lds_max_box`` (0..``DEBLEND_MAX_BOX``, with ``large_parents=True`` only)
+    moves the border between the two kernels; 0 sends every segment through
+    the global-memory one.  ``mode='sinh'`` and ``relabel=False`` raise
+    ``ValueError``."""
     seg = segment_img.data if isinstance(segment_img, SegmentationImage) else segment_img
     check_deblend_args(_shape_of(data), _shape_of(seg), npixels, nlevels, contrast, mode,
-                       connectivity, relabel)
+                       connectivity, relabel, large_parents, lds_max_box)
     _B.require_gpu()
     d, batched = _to_dev(data, keep_f32=False)
     lab, n = _labels_dev(segment_img, batched)
@@ -394,7 +424,8 @@ def deblend_sources(data, segment_img, npixels, labels=None, nlevels=32, contras
             raise ValueError(f"labels must lie in 1..{top}, got {labels!r}")
         select = np.zeros((d.shape[0], max(1, int(n.max()))), dtype=bool)
         select[:, want - 1] = True  # an image of a batch without such a label has no such row
-    res = _deblend_dev(d, lab, n, npixels, nlevels, contrast, mode, connectivity, select)
+    res = _deblend_dev(d, lab, n, npixels, nlevels, contrast, mode, connectivity, select,
+                       bool(large_parents), int(lds_max_box))
     return _deblended_image(res, batched, device_out)
 
 
@@ -404,12 +435,16 @@ class SourceFinder:
     (restoration/utils.py:235): ``finder(data, threshold, mask=None)`` is
     :func:`detect_sources` followed, when ``deblend``, by
     :func:`deblend_sources`.  ``relabel``, ``nproc`` and ``progress_bar`` are
-    accepted for the signature; ``nproc`` and ``progress_bar`` are ignored."""
+    accepted for the signature; ``nproc`` and ``progress_bar`` are ignored.
+    ``large_parents`` as in :func:`deblend_sources`."""
 
     def __init__(self, npixels, connectivity=8, deblend=True, nlevels=32, contrast=0.001,
-                 mode="exponential", relabel=True, nproc=1, progress_bar=True, device_out=False):
+                 mode="exponential", relabel=True, nproc=1, progress_bar=True, device_out=False,
+                 large_parents=False):
         check_detect_args((1, 1), npixels, connectivity)
-        check_deblend_args((1, 1), (1, 1), npixels, nlevels, contrast, mode, connectivity, relabel)
+        check_deblend_args((1, 1), (1, 1), npixels, nlevels, contrast, mode, connectivity, relabel,
+                           large_parents)
+        self.large_parents = bool(large_parents)
         self.npixels, self.connectivity, self.deblend = int(npixels), int(connectivity), bool(deblend)
         self.nlevels, self.contrast, self.mode = int(nlevels), float(contrast), mode
         self.device_out = device_out
@@ -426,7 +461,9 @@ class SourceFinder:
         if self.deblend:
             return _deblended_image(_deblend_dev(d.to(_B.torch.float64), lab, n, self.npixels,
                                                  self.nlevels, self.contrast, self.mode,
-                                                 self.connectivity), batched, self.device_out)
+                                                 self.connectivity,
+                                                 large_parents=self.large_parents),
+                                    batched, self.device_out)
         return SegmentationImage(_out(lab, batched, self.device_out), n, batched)
 
 
@@ -551,7 +588,7 @@ class SourceCatalog:
 
 
 def source_info(data, box_size, n_pixels=5, sigma_threshold=1.5, device_out=False, deblend=False,
-                nlevels=32, contrast=0.001):
+                nlevels=32, contrast=0.001, large_parents=False):
     """``utils.source_info`` (restoration/utils.py:235-247) for an image or a
     batch, with its deblending on request: ``Background2D(data, box_size,
     filter_size=(3, 3))``, ``sub = data - background``, ``threshold =
@@ -563,6 +600,8 @@ def source_info(data, box_size, n_pixels=5, sigma_threshold=1.5, device_out=Fals
     mode 'exponential'), and the catalogue of ``sub`` with
     ``convolved_data=conv``.  The default ``deblend=False`` gives the same sum
     of ``segment_flux`` and the columns of undeblended segments.
+    ``large_parents=True`` also deblends the segments whose box is over
+    ``DEBLEND_MAX_BOX`` (crowded cores), as in :func:`deblend_sources`.
     Returns ``(catalog, bkg)``; the catalogue also carries ``segment_img``,
     ``data`` (sub) and ``convolved_data``.  An unbatched image without a
     detection warns and gives ``(None, bkg)``.  With ``device_out=True`` the
@@ -571,7 +610,8 @@ def source_info(data, box_size, n_pixels=5, sigma_threshold=1.5, device_out=Fals
     torch = _B.torch
     _check_image_shape(_shape_of(data))
     check_detect_args(_shape_of(data), n_pixels, 8)
-    check_deblend_args(_shape_of(data), _shape_of(data), n_pixels, nlevels, contrast)
+    check_deblend_args(_shape_of(data), _shape_of(data), n_pixels, nlevels, contrast,
+                       large_parents=large_parents)
     bkg = Background2D(data, box_size, filter_size=(3, 3), device_out=True)
     d, batched = _to_dev(data)
     bg = bkg.background if batched else bkg.background[None]
@@ -590,7 +630,8 @@ def source_info(data, box_size, n_pixels=5, sigma_threshold=1.5, device_out=Fals
         return None, bkg
     seg = None
     if deblend:
-        res = _deblend_dev(conv, lab, n, int(n_pixels), nlevels, contrast, "exponential", 8)
+        res = _deblend_dev(conv, lab, n, int(n_pixels), nlevels, contrast, "exponential", 8,
+                           large_parents=bool(large_parents))
         seg, (lab, n) = _deblended_image(res, batched, device_out), res[:2]
     cat = SourceCatalog.__new__(SourceCatalog)
     cat._fill(sub, conv, lab, n.astype(np.int32), batched, device_out)

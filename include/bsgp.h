@@ -491,6 +491,25 @@ int bsgp_deblend_sources(const double* data, const int32_t* labels, int32_t B, i
                          const uint8_t* select, int32_t npixels, int32_t nlevels, double contrast,
                          int32_t mode, int32_t connectivity, int32_t* labels_out,
                          int32_t* nlabels_out, int32_t* status_out, void* stream);
+/* bsgp_deblend_sources with a second path for the parents it leaves: a parent
+ * whose box holds at most lds_max_box pixels (0 .. BSGP_DEBLEND_MAX_BOX, else
+ * BSGP_ERR_ARG) is deblended in LDS as above; every other parent by a kernel
+ * that keeps its working set in global memory (one workgroup per parent, the
+ * same steps D1 to D7, identities, orders and arithmetic, so a parent gets the
+ * same labels from either path; lds_max_box = 0 sends every parent through the
+ * global path).  Only a parent of more than BSGP_DEBLEND_LARGE_MAX_AREA pixels
+ * is left as it is and sets BSGP_DEBLEND_OVER_CAP: its flood runs on one lane,
+ * and the bound keeps that lane's work bounded.  The workspace, 32 bytes per
+ * pixel of the batch, is stream-ordered and depends on B, H and
+ * W only; the call stays asynchronous.  Everything else as
+ * bsgp_deblend_sources. */
+#define BSGP_DEBLEND_LARGE_MAX_AREA 262144
+int bsgp_deblend_sources_large(const double* data, const int32_t* labels, int32_t B, int32_t H,
+                               int32_t W, int32_t cap, const int32_t* nlabels,
+                               const int32_t* int_cols, const uint8_t* select, int32_t npixels,
+                               int32_t nlevels, double contrast, int32_t mode,
+                               int32_t connectivity, int32_t lds_max_box, int32_t* labels_out,
+                               int32_t* nlabels_out, int32_t* status_out, void* stream);
 
 /* Star-stamp metrics: what application_sgp_star_stamps.py:117-142
  * computes for the observed and the restored stamp.  All three are

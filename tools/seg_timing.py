@@ -18,7 +18,17 @@ parent, no parent selected (the fixed cost: numbering and relabel), only the
 parents that split and only those that do not; only a split parent runs the
 single-lane flood, so the last two bound its share.  A last line times the
 measurement of an all-true 2048x2048 image, whose one segment is scanned by a
-single wave.
+single wave.  The same deblend call is also made through
+bsgp_deblend_sources_large with the LDS cap where it is: these workloads hold
+no parent over the cap, so the difference is the added launch and the
+32 bytes per pixel of stream-ordered workspace.
+
+The crowded 450 x 450 frame (tests/golden/crowded_inputs.npz, source_info with
+box 60 and n_pixels 5) has parents over the LDS cap: its deblend stage is timed
+with the global-memory path off (bsgp_deblend_sources: those parents are left)
+and on (bsgp_deblend_sources_large), with only the parents over the cap, with
+the largest of them alone, and beside tests/deblend_ref.py on the host for the
+parents over the cap.
 
     python tools/seg_timing.py --out profiles/seg/timing.json
 """
@@ -158,7 +168,17 @@ def run(name, shape, box, host_images, rng, npix=5, sigma_threshold=1.5):
                                        B.BSGP_DEBLEND_EXPONENTIAL, 8, B._ptr(lab2), B._ptr(nlab2),
                                        B._ptr(dst), s()))
 
+    def deblend_large_entry():
+        B.check(L.bsgp_deblend_sources_large(B._ptr(conv), B._ptr(lab), n, H, W, cap, B._ptr(nlab),
+                                             B._ptr(ic), None, npix, 32, 0.001,
+                                             B.BSGP_DEBLEND_EXPONENTIAL, 8, B.BSGP_DEBLEND_MAX_BOX,
+                                             B._ptr(lab2), B._ptr(nlab2), B._ptr(dst), s()))
+
     t_deb, t_deb_all = timed(deblend)
+    first = lab2.clone()
+    t_deb_le, t_deb_le_all = timed(deblend_large_entry)
+    assert torch.equal(first, lab2) and not dst.cpu().numpy().any()
+    t_deb, t_deb_all = timed(deblend)  # once more after the other: the pair is taken in one run
     counts2 = nlab2.cpu().numpy()
     over = int((dst.cpu().numpy() & B.BSGP_DEBLEND_OVER_CAP != 0).sum())
     # parent of every output label, hence the parents that split
@@ -199,6 +219,9 @@ def run(name, shape, box, host_images, rng, npix=5, sigma_threshold=1.5):
         "ms_detect_labelling_and_compaction": t_det, "ms_detect_all": t_det_all,
         "ms_measure": t_cat, "ms_all_stages_one_after_another": t_all, "ms_all_stages_all": t_all_all,
         "ms_deblend": t_deb, "ms_deblend_all": t_deb_all,
+        "ms_deblend_through_the_large_entry_point": t_deb_le,
+        "ms_deblend_through_the_large_entry_point_all": t_deb_le_all,
+        "large_entry_point_workspace_bytes": 32 * n * H * W,
         "ms_deblend_no_parent_selected": t_none, "ms_deblend_only_parents_that_split": t_split,
         "ms_deblend_only_parents_that_do_not_split": t_rest,
         "deblend_parents_of_at_least_2_npixels": can_split, "deblend_parents_split": int(split.sum().item()),
@@ -236,6 +259,78 @@ def all_true(H=2048, W=2048):
     return r
 
 
+def crowded(npix=5):
+    """The deblend stage of the crowded frame with the global-memory path off and on."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import deblend_ref
+    with np.load(os.path.join(ROOT, "tests", "golden", "crowded_inputs.npz")) as f:
+        img = f["img"].astype(np.float32)
+    H, W = img.shape
+    L = B.lib()
+    cat, _ = S.source_info(img, 60, npix, device_out=True)
+    conv = cat.convolved_data.reshape(1, H, W).contiguous()
+    lab = cat.segment_img.data.reshape(1, H, W).contiguous()
+    ic = cat.int_cols.contiguous()
+    cap = ic.shape[1]
+    i32 = dict(dtype=torch.int32, device="cuda")
+    nlab = torch.tensor([cat.nlabels], **i32)
+    lab2, nlab2, dst = torch.empty((1, H, W), **i32), torch.empty((1,), **i32), torch.empty((1,), **i32)
+    s = B.current_stream
+
+    def call(large, select=None):
+        head = (B._ptr(conv), B._ptr(lab), 1, H, W, cap, B._ptr(nlab), B._ptr(ic), B._ptr(select),
+                npix, 32, 0.001, B.BSGP_DEBLEND_EXPONENTIAL, 8)
+        tail = (B._ptr(lab2), B._ptr(nlab2), B._ptr(dst), s())
+        if large:
+            B.check(L.bsgp_deblend_sources_large(*head, B.BSGP_DEBLEND_MAX_BOX, *tail))
+        else:
+            B.check(L.bsgp_deblend_sources(*head, *tail))
+
+    ich = ic.cpu().numpy()[0]
+    box = (ich[:, 2] - ich[:, 1] + 1).astype(np.int64) * (ich[:, 4] - ich[:, 3] + 1)
+    over = np.flatnonzero((box > B.BSGP_DEBLEND_MAX_BOX) & (ich[:, 0] >= 2 * npix))
+    assert len(over), "no parent over the cap"
+    largest = over[np.argmax(ich[over, 0])]
+
+    def select(rows):
+        m = np.zeros((1, cap), np.uint8)
+        m[0, rows] = 1
+        return torch.from_numpy(m).cuda()
+
+    t_off, t_off_all = timed(lambda: call(False))
+    n_off, flagged = int(nlab2.cpu()[0]), int(dst.cpu()[0])
+    t_on, t_on_all = timed(lambda: call(True))
+    n_on = int(nlab2.cpu()[0])
+    assert flagged == B.BSGP_DEBLEND_OVER_CAP and int(dst.cpu()[0]) == 0
+    sel_over, sel_one, sel_under = select(over), select([largest]), select(np.setdiff1d(np.arange(cap), over))
+    t_over, _ = timed(lambda: call(True, sel_over))
+    t_one, _ = timed(lambda: call(True, sel_one))
+    t_under, _ = timed(lambda: call(True, sel_under))
+    call(True, sel_over)
+    got = lab2.cpu().numpy()[0]
+    ch, lh = conv.cpu().numpy()[0], lab.cpu().numpy()[0]
+    t0 = time.perf_counter()
+    ref, _, st = deblend_ref.deblend(ch, lh, npix, labels=[int(l) + 1 for l in over])
+    host_s = time.perf_counter() - t0
+    assert np.array_equal(got, ref)
+    r = {"workload": f"crowded frame {H}x{W}, box 60", "n_pixels": npix, "segments": int(cat.nlabels),
+         "parents_over_the_lds_cap": len(over),
+         "their_boxes": [int(b) for b in box[over]], "their_areas": [int(a) for a in ich[over, 0]],
+         "fraction_of_detected_pixels_in_them": float(ich[over, 0].sum() / ich[:, 0].sum()),
+         "children_of_them": int(st["nchildren"]), "region_replacements": int(st["splits"]),
+         "contrast_removals": int(st["removals"]),
+         "labels_out_large_parents_off": n_off, "labels_out_large_parents_on": n_on,
+         "ms_deblend_large_parents_off": t_off, "ms_deblend_large_parents_off_all": t_off_all,
+         "ms_deblend_large_parents_on": t_on, "ms_deblend_large_parents_on_all": t_on_all,
+         "ms_deblend_only_parents_over_the_cap": t_over,
+         "ms_deblend_only_parents_under_the_cap_large_entry": t_under,
+         "ms_deblend_largest_parent_alone": t_one, "largest_parent_area": int(ich[largest, 0]),
+         "largest_parent_box": int(box[largest]),
+         "host_restatement_of_parents_over_the_cap_s": host_s}
+    print(json.dumps(r))
+    return r
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -244,7 +339,7 @@ def main():
     rng = np.random.default_rng(0)
     res = [run("field 2048^2, box 64", (1, 2048, 2048), 64, 1, rng),
            run("1024 x 256^2, box 32", (1024, 256, 256), 32, 32, rng),
-           all_true()]
+           all_true(), crowded()]
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
