@@ -38,6 +38,8 @@ BSGP_DEBLEND_MAX_BOX = 4096  # box pixels of one parent in LDS (include/bsgp.h)
 BSGP_DEBLEND_LARGE_MAX_AREA = 262144  # pixels of one parent on the global-memory path
 BSGP_DEBLEND_LINEAR, BSGP_DEBLEND_EXPONENTIAL = 0, 1
 BSGP_DEBLEND_OVER_CAP, BSGP_DEBLEND_BAD_LABEL = 1, 2
+BSGP_LOCALBKG_MAX = 8192  # values of one local-background annulus in LDS (include/bsgp.h)
+BSGP_LOCALBKG_FEW, BSGP_LOCALBKG_OVER_CAP = 1, 2
 
 
 class BsgpError(RuntimeError):
@@ -175,6 +177,9 @@ def lib():
                                                i32, i32, vp, vp, vp, vp]
             L.bsgp_deblend_sources_large.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp, i32,
                                                      i32, dbl, i32, i32, i32, vp, vp, vp, vp]
+            L.bsgp_segment_local_background.argtypes = [vp, i32, vp, i32, i32, i32, i32, vp, vp,
+                                                        vp, dbl, dbl, i32, i32, i32, vp, vp, vp,
+                                                        vp]
             L.bsgp_radial_profile.argtypes = [vp, i32, i32, i32, i32, vp, i32, vp, vp, vp]
             L.bsgp_fit_gauss1d.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]
             L.bsgp_wasserstein1.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp]
@@ -190,7 +195,7 @@ def lib():
                          "bsgp_segment_catalog", "bsgp_plan_set_static_geo",
                          "bsgp_plan_static_geo", "bsgp_radial_profile", "bsgp_fit_gauss1d",
                          "bsgp_wasserstein1", "bsgp_deblend_sources",
-                         "bsgp_deblend_sources_large"]:
+                         "bsgp_deblend_sources_large", "bsgp_segment_local_background"]:
                 getattr(L, name).restype = ctypes.c_int
             if L.bsgp_abi_version() != ABI_VERSION:
                 raise BsgpError(-3, f"{LIB_PATH} has ABI {L.bsgp_abi_version()}, this binding "
@@ -208,7 +213,7 @@ EXPORTED = ["bsgp_plan_create", "bsgp_plan_create_checked", "bsgp_plan_destroy",
             "bsgp_convolve2d", "bsgp_detect_sources", "bsgp_segment_catalog",
             "bsgp_plan_set_static_geo", "bsgp_plan_static_geo", "bsgp_radial_profile",
             "bsgp_fit_gauss1d", "bsgp_wasserstein1", "bsgp_deblend_sources",
-            "bsgp_deblend_sources_large"]
+            "bsgp_deblend_sources_large", "bsgp_segment_local_background"]
 
 
 def check(rc):

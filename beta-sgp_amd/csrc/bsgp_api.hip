@@ -1680,6 +1680,41 @@ int bsgp_segment_catalog(const double* data, const double* conv, const int32_t* 
   return BSGP_OK;
 }
 
+int bsgp_segment_local_background(const void* data, int32_t dtype, const int32_t* labels, int32_t B,
+                                  int32_t H, int32_t W, int32_t cap, const int32_t* nlabels,
+                                  const int32_t* int_cols, double* f64_cols,
+                                  double localbkg_width, double sigma, int32_t maxiters,
+                                  int32_t min_pixels, int32_t apply, double* lb_out,
+                                  int32_t* npix_out, int32_t* status_out, void* stream) {
+  if (!(localbkg_width > 0.0) || !std::isfinite(localbkg_width))
+    return fail(BSGP_ERR_ARG, "localbkg_width must be finite and > 0");
+  if (!(sigma > 0.0)) return fail(BSGP_ERR_ARG, "sigma must be > 0");
+  if (maxiters < 0) return fail(BSGP_ERR_ARG, "maxiters must be >= 0");
+  if (min_pixels < 1) return fail(BSGP_ERR_ARG, "min_pixels must be >= 1");
+  if (dtype != BSGP_DTYPE_F32 && dtype != BSGP_DTYPE_F64)
+    return fail(BSGP_ERR_ARG, "dtype must be BSGP_DTYPE_F32 or BSGP_DTYPE_F64");
+  if (cap < 1) return fail(BSGP_ERR_ARG, "cap must be >= 1");
+  if (B == 0) return BSGP_OK;  // no image: nothing to do, no pointer is followed
+  if (!data) return fail(BSGP_ERR_ARG, "data is NULL");
+  if (!labels || !int_cols) return fail(BSGP_ERR_ARG, "labels / int_cols is NULL");
+  if (apply && !f64_cols) return fail(BSGP_ERR_ARG, "f64_cols is NULL (apply != 0)");
+  if (!lb_out || !npix_out || !status_out)
+    return fail(BSGP_ERR_ARG, "lb_out / npix_out / status_out is NULL");
+  if (int rc = seg_shape(B, H, W)) return rc;
+  LocalBkgArgs a{};
+  a.data = data, a.labels = labels, a.nlabels = nlabels, a.icols = int_cols, a.fcols = f64_cols;
+  a.B = B, a.H = H, a.W = W, a.cap = cap, a.maxiters = maxiters, a.min_pixels = min_pixels;
+  a.apply = apply ? 1 : 0, a.width = localbkg_width, a.sigma = sigma;
+  a.lb = lb_out, a.npix = npix_out, a.status = status_out;
+  hipStream_t s = (hipStream_t)stream;
+  const size_t rows = (size_t)B * cap;
+  HIP_TRY(hipMemsetAsync(lb_out, 0, rows * sizeof(double), s));
+  HIP_TRY(hipMemsetAsync(npix_out, 0, 2 * rows * sizeof(int), s));
+  HIP_TRY(hipMemsetAsync(status_out, 0, (size_t)B * sizeof(int), s));
+  HIP_TRY(launch_localbkg(a, dtype == BSGP_DTYPE_F32, s));
+  return BSGP_OK;
+}
+
 // both deblending entry points; lds_max_box < 0: bsgp_deblend_sources (no global-memory path)
 static int deblend_sources(const double* data, const int32_t* labels, int32_t B, int32_t H, int32_t W,
                            int32_t cap, const int32_t* nlabels, const int32_t* int_cols,

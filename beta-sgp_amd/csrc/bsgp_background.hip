@@ -26,13 +26,11 @@
 #include <cmath>
 
 #include "bsgp_internal.hpp"
+#include "bsgp_sigclip.hpp"
 
 namespace bsgp {
 
 namespace {
-
-__device__ __forceinline__ double bkg_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
-__device__ __forceinline__ double bkg_inf() { return __longlong_as_double(0x7ff0000000000000LL); }
 
 // min and max of one value per thread over the workgroup, in every thread
 __device__ __forceinline__ void block_minmax(double& mn, double& mx, double* red) {
@@ -51,24 +49,6 @@ __device__ __forceinline__ void block_minmax(double& mn, double& mx, double* red
     mx = red[kWaves + k] > mx ? red[kWaves + k] : mx;
   }
   __syncthreads();
-}
-
-// ascending bitonic sort of s[0, P) in LDS, P a power of two, 256 threads
-__device__ __forceinline__ void bkg_sort(double* s, int P) {
-  for (int k = 2; k <= P; k <<= 1) {
-    for (int jj = k >> 1; jj > 0; jj >>= 1) {
-      for (int t = threadIdx.x; t < (P >> 1); t += 256) {
-        const int lo_i = 2 * t - (t & (jj - 1)), hi_i = lo_i + jj;
-        const bool up = (lo_i & k) == 0;
-        const double x = s[lo_i], y = s[hi_i];
-        if ((x > y) == up) {
-          s[lo_i] = y;
-          s[hi_i] = x;
-        }
-      }
-      __syncthreads();
-    }
-  }
 }
 
 }  // namespace
@@ -124,56 +104,14 @@ __global__ void __launch_bounds__(256) k_bkg_boxstats(BkgArgs a) {
 
   bkg_sort(s, P);
 
-  // sigma clipping on the sorted range [lo, hi)
-  int lo = 0, hi = nvalid, it = 0;
-  bool more = a.maxiters > 0;
-  double med, sd;
-  for (;;) {
-    const int n = hi - lo;
-    med = (n & 1) ? s[lo + n / 2] : (s[lo + n / 2 - 1] + s[lo + n / 2]) / 2.0;
-    double v[1] = {0.0};
-    for (int k = lo + tid; k < hi; k += 256) v[0] += s[k];
-    block_sum<1>(v, red);
-    const double mean = v[0] / (double)n;
-    v[0] = 0.0;
-    for (int k = lo + tid; k < hi; k += 256) {
-      const double d = s[k] - mean;
-      v[0] += d * d;
-    }
-    block_sum<1>(v, red);
-    sd = sqrt(v[0] / (double)n);
-    if (!more) break;
-    const double lb = med - sd * a.sigma, ub = med + sd * a.sigma;
-    int l = lo, r = hi;
-    while (l < r) {  // first value >= lb
-      const int m = (l + r) >> 1;
-      if (s[m] < lb) l = m + 1; else r = m;
-    }
-    const int nlo = l;
-    r = hi;
-    while (l < r) {  // first value > ub
-      const int m = (l + r) >> 1;
-      if (s[m] <= ub) l = m + 1; else r = m;
-    }
-    const int nhi = l;
-    ++it;
-    if (nhi <= nlo) {  // a sigma so small that nothing is left: NaN, as numpy of no values
-      lo = hi = nlo;
-      med = sd = bkg_nan();
-      break;
-    }
-    const bool changed = nlo != lo || nhi != hi;
-    lo = nlo;
-    hi = nhi;
-    if (!changed) break;
-    more = it < a.maxiters;
-  }
+  // sigma clipping on the sorted range [lo, hi) (bsgp_sigclip.hpp)
+  const SigClip c = sigma_clip_sorted(s, nvalid, a.sigma, a.maxiters, red);
   if (tid == 0) {
-    raw[cell] = med;
-    raw[ncell + cell] = sd;
+    raw[cell] = c.med;
+    raw[ncell + cell] = c.sd;
     wi[cell] = 0;
-    wi[ncell + cell] = hi - lo;
-    wi[2 * ncell + cell] = it;
+    wi[ncell + cell] = c.hi - c.lo;
+    wi[2 * ncell + cell] = c.it;
   }
 }
 

@@ -194,6 +194,21 @@ struct SegCatArgs {
 hipError_t launch_seg_convolve(const SegConvArgs& a, int f32, hipStream_t s);
 hipError_t launch_seg_detect(const SegArgs& a, int f32, hipStream_t s);
 hipError_t launch_seg_catalog(const SegCatArgs& a, hipStream_t s);
+// ---- local background (bsgp_localbkg.hip) ------------
+constexpr int kLocalBkgMax = BSGP_LOCALBKG_MAX;  // values of one annulus: 64 KiB of LDS
+struct LocalBkgArgs {
+  const void* data;    // [B][H][W] float32 or float64
+  const int* labels;   // [B][H][W]
+  const int* nlabels;  // [B], or nullptr: cap
+  const int* icols;    // [B][cap][5] as bsgp_segment_catalog writes them
+  double* fcols;       // [B][cap][8]: flux, min, max corrected in place when apply
+  int B, H, W, cap, maxiters, min_pixels, apply;
+  double width, sigma;
+  double* lb;   // [B][cap] (zeroed first)
+  int* npix;    // [B][cap][2]: values gathered, survivors (zeroed first)
+  int* status;  // [B]: BSGP_LOCALBKG_* bits (zeroed first)
+};
+hipError_t launch_localbkg(const LocalBkgArgs& a, int f32, hipStream_t s);
 // ---- deblending (bsgp_deblend.hip) -----------------------------
 constexpr int kDeblendMaxBox = BSGP_DEBLEND_MAX_BOX;  // box pixels of one parent (LDS)
 struct DeblendArgs {

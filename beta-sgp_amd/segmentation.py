@@ -19,11 +19,21 @@ removal of small components and a consecutive relabel, which is photutils'
 documented ``deblend_sources`` and pinned to the parts it is built from,
 ``scipy.ndimage.label`` and ``skimage.segmentation.watershed`` (DESIGN §3.8,
 steps D1 to D7).  It splits a segment among children without dropping a pixel,
-so the sum of ``segment_flux`` over all segments -- the quantity the flux
-constraint and the score use -- is the same with and without it;
-``source_info`` therefore deblends only on request (``deblend=True``), for the
-per-source columns.  The moment and shape columns are defined in DESIGN §3.8,
-modelled on photutils' documentation but not pinned to it.
+so at ``localbkg_width=0`` the sum of ``segment_flux`` over all segments is
+the same with and without it; ``source_info`` therefore deblends only on
+request (``deblend=True``).  The moment and shape columns are defined in
+DESIGN §3.8, modelled on photutils' documentation but not pinned to it.
+
+The reference builds its catalogue with ``SourceCatalog(...,
+localbkg_width=5)`` (utils.py:244-246): photutils measures a local background
+in a rectangular annulus around every source and subtracts it from
+``segment_flux``, ``min_value`` and ``max_value``.  ``localbkg_width > 0`` does
+the same here (``bsgp_segment_local_background``, DESIGN §3.8 L1 to L6,
+modelled on photutils and pinned to the catalogue the reference published for
+its frame).  Then every segment has its own box, annulus and area, so the sum
+over segments depends on the deblending: the reference's flux constraint is
+``localbkg_width=5`` together with ``deblend=True``.  The default is 0
+everywhere, which leaves the columns as they were.
 """
 import warnings
 
@@ -42,7 +52,8 @@ SHAPE_COLUMNS = ("semimajor_sigma", "semiminor_sigma", "orientation", "eccentric
 COLUMNS = ("label",) + INT_COLUMNS + F64_COLUMNS + SHAPE_COLUMNS
 UNAVAILABLE = {
     "sky_centroid": "there is no WCS here: use xcentroid / ycentroid",
-    "local_background": "data is background-subtracted; no local annulus is measured",
+    "local_background": "no local background was measured: pass localbkg_width > 0 "
+                        "(photutils' localbkg_width; the reference uses 5)",
     "segment_fluxerr": "no error array is carried: photometric errors are out of scope",
 }
 
@@ -57,7 +68,14 @@ class DeblendBoxWarning(UserWarning):
     DEBLEND_LARGE_MAX_AREA pixels): it is left undeblended."""
 
 
+class LocalBackgroundCapWarning(UserWarning):
+    """The local-background annulus of a source holds more than LOCALBKG_MAX
+    values: its local background is 0 and its columns are left uncorrected."""
+
+
 DEBLEND_MAX_BOX = _B.BSGP_DEBLEND_MAX_BOX
+LOCALBKG_MAX = _B.BSGP_LOCALBKG_MAX
+LOCALBKG_SIGMA, LOCALBKG_MAXITERS, LOCALBKG_MIN_PIXELS = 3.0, 10, 10  # photutils' constants
 DEBLEND_LARGE_MAX_AREA = _B.BSGP_DEBLEND_LARGE_MAX_AREA
 DEBLEND_MODES = {"linear": _B.BSGP_DEBLEND_LINEAR, "exponential": _B.BSGP_DEBLEND_EXPONENTIAL}
 
@@ -135,6 +153,16 @@ def _dtype(d):
 def _out(t, batched, device_out):
     t = t if batched else t[0]
     return t if device_out else t.cpu().numpy()
+
+
+def check_localbkg_width(localbkg_width):
+    """The argument check of ``localbkg_width`` (host only): a finite number
+    >= 0 (photutils takes an int; any finite width is served)."""
+    w = localbkg_width
+    if isinstance(w, (bool, np.bool_)) or not isinstance(w, (int, float, np.integer, np.floating)) \
+            or not np.isfinite(w) or w < 0:
+        raise ValueError(f"localbkg_width must be a finite number >= 0, got {localbkg_width!r}")
+    return float(w)
 
 
 def convolve(data, kernel, device_out=False):
@@ -486,7 +514,8 @@ def shape_columns(sigx2, sigxy, sigy2):
 
 
 class SourceCatalog:
-    """``SourceCatalog(data, segment_img, convolved_data=None)`` on the device.
+    """``SourceCatalog(data, segment_img, convolved_data=None, localbkg_width=0)``
+    on the device.
 
     ``data`` is already background-subtracted, as ``source_info`` passes it
     (``background`` is accepted for photutils' signature and only kept).
@@ -499,17 +528,30 @@ class SourceCatalog:
     of ``data`` without one) and from those ``semimajor_sigma``,
     ``semiminor_sigma``, ``orientation`` (degrees), ``eccentricity``,
     ``ellipticity``, ``fwhm`` (:func:`shape_columns`).  ``segment_flux_sum`` is
-    the sum over all segments -- the deblend-invariant quantity the
-    application uses -- per image.  The columns describe the segments of
+    the numpy sum of ``segment_flux`` over all segments per image -- what the
+    application uses; at ``localbkg_width=0`` deblending does not change it.  The columns describe the segments of
     ``segment_img``, deblended or not; the moment and shape columns are modelled on photutils, not pinned to it.
-    ``sky_centroid``, ``local_background`` and ``segment_fluxerr`` raise
-    ``KeyError`` with the reason.  ``device_out=True`` adds ``int_cols`` /
-    ``f64_cols`` (CUDA tensors [B, cap, 5] / [B, cap, 8])."""
+    ``localbkg_width > 0`` (photutils' parameter; the reference passes 5) adds
+    the column ``local_background`` -- SExtractor's mode of the sigma-clipped
+    unlabelled pixels of a rectangular annulus of that width around the
+    source's box -- and subtracts it from
+    ``segment_flux`` (times ``area``), ``min_value`` and ``max_value``; the
+    other columns are unaffected.  A source with fewer than 10 annulus values
+    gets 0.0; one with more than ``LOCALBKG_MAX`` gets 0.0, no correction and a
+    :class:`LocalBackgroundCapWarning`; ``localbkg_status`` holds the
+    ``BSGP_LOCALBKG_*`` bits per image and ``localbkg_npix`` [n, 2] the annulus
+    values gathered and those the clipping left, per source.  At the default 0 ``local_background``
+    raises ``KeyError``; ``sky_centroid`` and ``segment_fluxerr`` always do,
+    with the reason.  ``device_out=True`` adds ``int_cols`` / ``f64_cols`` (CUDA
+    tensors [B, cap, 5] / [B, cap, 8]) and, with a width,
+    ``local_background_dev`` [B, cap]."""
 
-    def __init__(self, data, segment_img, convolved_data=None, background=None, device_out=False):
+    def __init__(self, data, segment_img, convolved_data=None, background=None, device_out=False,
+                 localbkg_width=0):
         torch = _B.torch
         shape = _shape_of(data)
         _check_image_shape(shape)
+        width = check_localbkg_width(localbkg_width)
         seg = segment_img.data if isinstance(segment_img, SegmentationImage) else segment_img
         if _shape_of(seg) != shape:
             raise ValueError(f"segment_img shape {_shape_of(seg)} does not match data shape {shape}")
@@ -528,10 +570,10 @@ class SourceCatalog:
             if bool((lab < 0).any()):
                 raise ValueError("segment_img holds negative labels")
             n = lab.reshape(lab.shape[0], -1).amax(dim=1).cpu().numpy().astype(np.int32)
-        self._fill(d, c, lab, n, batched, device_out)
+        self._fill(d, c, lab, n, batched, device_out, width)
         self.background = background
 
-    def _fill(self, d, c, lab, n, batched, device_out):
+    def _fill(self, d, c, lab, n, batched, device_out, localbkg_width=0.0):
         torch = _B.torch
         B, H, W = d.shape
         cap = max(1, int(n.max()))
@@ -542,6 +584,16 @@ class SourceCatalog:
         _B.check(_B.lib().bsgp_segment_catalog(_B._ptr(d), _B._ptr(c), _B._ptr(lab), B, H, W, cap,
                                                _B._ptr(nd), _B._ptr(ic), _B._ptr(fc), _B._ptr(st),
                                                _B.current_stream()))
+        lbd = None
+        if localbkg_width > 0:  # L1 to L6: corrects fc in place (stream-ordered after the catalogue)
+            lbd = torch.empty((B, cap), dtype=torch.float64, device="cuda")
+            npx = torch.empty((B, cap, 2), dtype=torch.int32, device="cuda")
+            lst = torch.empty((B,), dtype=torch.int32, device="cuda")
+            _B.check(_B.lib().bsgp_segment_local_background(
+                _B._ptr(d), _dtype(d), _B._ptr(lab), B, H, W, cap, _B._ptr(nd), _B._ptr(ic),
+                _B._ptr(fc), float(localbkg_width), LOCALBKG_SIGMA, LOCALBKG_MAXITERS,
+                LOCALBKG_MIN_PIXELS, 1, _B._ptr(lbd), _B._ptr(npx), _B._ptr(lst),
+                _B.current_stream()))
         ich, fch, sth = ic.cpu().numpy(), fc.cpu().numpy(), st.cpu().numpy()
         if sth.any():
             raise _B.BsgpError(_B.BSGP_ERR_ARG, f"image {int(np.flatnonzero(sth)[0])}: labels "
@@ -557,6 +609,20 @@ class SourceCatalog:
         shp = [shape_columns(fch[b, :n[b], 5], fch[b, :n[b], 6], fch[b, :n[b], 7]) for b in range(B)]
         for nm in SHAPE_COLUMNS:
             cols[nm] = [s[nm] for s in shp]
+        self.localbkg_width = localbkg_width
+        if lbd is not None:
+            lbh, nph, lsh = lbd.cpu().numpy(), npx.cpu().numpy(), lst.cpu().numpy()
+            cols["local_background"] = [lbh[b, :n[b]] for b in range(B)]
+            npl = [nph[b, :n[b]] for b in range(B)]
+            self.localbkg_npix = npl if batched else npl[0]
+            self.localbkg_status = lsh if batched else int(lsh[0])
+            if device_out:
+                self.local_background_dev = lbd
+            if (lsh & _B.BSGP_LOCALBKG_OVER_CAP).any():
+                over = sum(int((v[:, 0] > LOCALBKG_MAX).sum()) for v in npl)
+                warnings.warn(f"{over} source(s) with a local-background annulus of more than "
+                              f"{LOCALBKG_MAX} values were left uncorrected (local_background 0)",
+                              LocalBackgroundCapWarning)
         self._cols = cols
         # one fixed order for the total as well: numpy's sum of the per-segment fluxes
         tot = np.array([float(np.sum(v)) for v in cols["segment_flux"]])
@@ -571,7 +637,7 @@ class SourceCatalog:
             raise AttributeError(str(e)) from None
 
     def __getitem__(self, name):
-        if name in UNAVAILABLE:
+        if name not in self._cols and name in UNAVAILABLE:
             raise KeyError(f"{name} is not available: {UNAVAILABLE[name]}")
         if name not in self._cols:
             raise KeyError(f"unknown column {name!r}; available: {', '.join(COLUMNS)}")
@@ -584,11 +650,12 @@ class SourceCatalog:
     def to_dict(self, columns=None):
         """The named columns (default: all) as a dict; unknown and unavailable
         names raise ``KeyError``."""
-        return {k: self[k] for k in (COLUMNS if columns is None else columns)}
+        every = COLUMNS + (("local_background",) if "local_background" in self._cols else ())
+        return {k: self[k] for k in (every if columns is None else columns)}
 
 
 def source_info(data, box_size, n_pixels=5, sigma_threshold=1.5, device_out=False, deblend=False,
-                nlevels=32, contrast=0.001, large_parents=False):
+                nlevels=32, contrast=0.001, large_parents=False, localbkg_width=0):
     """``utils.source_info`` (restoration/utils.py:235-247) for an image or a
     batch, with its deblending on request: ``Background2D(data, box_size,
     filter_size=(3, 3))``, ``sub = data - background``, ``threshold =
@@ -598,8 +665,11 @@ def source_info(data, box_size, n_pixels=5, sigma_threshold=1.5, device_out=Fals
     ``SourceFinder(npixels=n_pixels, deblend=True)``, i.e. ``deblend_sources(conv,
     segment_img, n_pixels, nlevels=nlevels, contrast=contrast)`` (connectivity 8,
     mode 'exponential'), and the catalogue of ``sub`` with
-    ``convolved_data=conv``.  The default ``deblend=False`` gives the same sum
-    of ``segment_flux`` and the columns of undeblended segments.
+    ``convolved_data=conv``.  At ``localbkg_width=0`` the default
+    ``deblend=False`` gives the same sum of ``segment_flux`` and the columns of
+    undeblended segments.  ``localbkg_width`` as in :class:`SourceCatalog`; the
+    reference's catalogue (utils.py:244-246) is ``localbkg_width=5`` with
+    ``deblend=True``, and with a width the sum depends on the deblending.
     ``large_parents=True`` also deblends the segments whose box is over
     ``DEBLEND_MAX_BOX`` (crowded cores), as in :func:`deblend_sources`.
     Returns ``(catalog, bkg)``; the catalogue also carries ``segment_img``,
@@ -612,6 +682,7 @@ def source_info(data, box_size, n_pixels=5, sigma_threshold=1.5, device_out=Fals
     check_detect_args(_shape_of(data), n_pixels, 8)
     check_deblend_args(_shape_of(data), _shape_of(data), n_pixels, nlevels, contrast,
                        large_parents=large_parents)
+    width = check_localbkg_width(localbkg_width)
     bkg = Background2D(data, box_size, filter_size=(3, 3), device_out=True)
     d, batched = _to_dev(data)
     bg = bkg.background if batched else bkg.background[None]
@@ -634,17 +705,22 @@ def source_info(data, box_size, n_pixels=5, sigma_threshold=1.5, device_out=Fals
                            large_parents=bool(large_parents))
         seg, (lab, n) = _deblended_image(res, batched, device_out), res[:2]
     cat = SourceCatalog.__new__(SourceCatalog)
-    cat._fill(sub, conv, lab, n.astype(np.int32), batched, device_out)
+    cat._fill(sub, conv, lab, n.astype(np.int32), batched, device_out, width)
     cat.background = None
     cat.segment_img = seg or SegmentationImage(_out(lab, batched, device_out), n, batched)
     cat.data, cat.convolved_data = _out(sub, batched, device_out), _out(conv, batched, device_out)
     return cat, bkg
 
 
-def segment_flux_sums(images, box_size, n_pixels=5, sigma_threshold=1.5):
+def segment_flux_sums(images, box_size, n_pixels=5, sigma_threshold=1.5, localbkg_width=0,
+                      deblend=False, large_parents=False):
     """Sum of ``segment_flux`` per image of a batch [B, H, W] (one batched
-    ``source_info``); 0.0 for an image without a detection."""
-    cat, _ = source_info(images, box_size, n_pixels, sigma_threshold, device_out=True)
+    ``source_info``); 0.0 for an image without a detection.  ``localbkg_width``,
+    ``deblend`` and ``large_parents`` as in :func:`source_info`
+    (``localbkg_width=5, deblend=True``: the reference's sum)."""
+    cat, _ = source_info(images, box_size, n_pixels, sigma_threshold, device_out=True,
+                         deblend=deblend, large_parents=large_parents,
+                         localbkg_width=localbkg_width)
     return np.asarray(cat.segment_flux_sum, dtype=np.float64)
 
 
@@ -658,13 +734,27 @@ def flux_fraction_score(gn, box_size=60, n_pixels_orig=5, n_pixels_restored=1,
     sum(segment_flux(source_info(gn or tile, box_size, n_pixels_orig)))``;
     ``score.batch(xs)`` / ``score.batch(xs, tiles)`` evaluate candidates
     [n, H, W] in one batched ``source_info`` (``tiles``: one observed image, or
-    one per candidate)."""
+    one per candidate).  The catalogues are those of ``localbkg_width=0``
+    without deblending; :func:`catalog_flux_fraction_score` takes both."""
+    return catalog_flux_fraction_score(gn, box_size, n_pixels_orig, n_pixels_restored,
+                                       sigma_threshold)
+
+
+def catalog_flux_fraction_score(gn, box_size=60, n_pixels_orig=5, n_pixels_restored=1,
+                                sigma_threshold=1.5, localbkg_width=0, deblend=False):
+    """:func:`flux_fraction_score` with the catalogue's keywords:
+    ``localbkg_width`` and ``deblend`` go to both ``source_info`` calls.  The
+    reference's score is ``localbkg_width=5, deblend=True`` (its catalogue
+    subtracts a local background, utils.py:244-246); the defaults give
+    :func:`flux_fraction_score`."""
+    check_localbkg_width(localbkg_width)
     cache = {}
+    kw = dict(localbkg_width=localbkg_width, deblend=deblend)
 
     def orig(img):
         """Flux sums of the observed image(s) [n, H, W] or [H, W] -> [n] or [1]."""
         a = img if len(_shape_of(img)) == 3 else img[None]
-        return segment_flux_sums(a, box_size, n_pixels_orig, sigma_threshold)
+        return segment_flux_sums(a, box_size, n_pixels_orig, sigma_threshold, **kw)
 
     def orig_gn():
         if "gn" not in cache:
@@ -675,7 +765,7 @@ def flux_fraction_score(gn, box_size=60, n_pixels_orig=5, n_pixels_restored=1,
 
     def batch(xs, tiles=None):
         den = orig_gn() if tiles is None else orig(tiles)
-        num = segment_flux_sums(xs, box_size, n_pixels_restored, sigma_threshold)
+        num = segment_flux_sums(xs, box_size, n_pixels_restored, sigma_threshold, **kw)
         return 1.0 - num / den
 
     def score(x, tile=None):

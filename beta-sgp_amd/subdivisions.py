@@ -135,12 +135,15 @@ def _estimate_bkg(image, bkg, box_size, filter_size):
     return Background2D(image, box_size, filter_size=filter_size, device_out=True).background
 
 
-def _segment_flux(sgp_kwargs, tiles, box_size, repeat=1):
+def _segment_flux(sgp_kwargs, tiles, box_size, repeat=1, localbkg_width=0, deblend=False):
     """``flux="segments"``: every tile's flux constraint becomes the sum of
-    ``segment_flux`` of ``source_info(tile, bkg_box_size, n_pixels=5)``
+    ``segment_flux`` of ``source_info(tile, bkg_box_size, n_pixels=5,
+    localbkg_width=localbkg_width, deblend=deblend)``
     (application_sgp_subdivisions.py:88,104,113: each subdivision's own
     detection with its own background), all tiles in one batch; any other
     ``flux`` stays as it is."""
+    from segmentation import check_localbkg_width
+    check_localbkg_width(localbkg_width)
     if not isinstance(sgp_kwargs.get("flux"), str):
         return
     if sgp_kwargs["flux"] != "segments":
@@ -148,11 +151,14 @@ def _segment_flux(sgp_kwargs, tiles, box_size, repeat=1):
     if box_size is None:
         raise ValueError('flux="segments" needs bkg_box_size (source_info\'s box_size)')
     from segmentation import segment_flux_sums
-    sgp_kwargs["flux"] = np.repeat(segment_flux_sums(tiles, box_size, n_pixels=5), repeat)
+    sums = segment_flux_sums(tiles, box_size, n_pixels=5, localbkg_width=localbkg_width,
+                             deblend=bool(deblend))
+    sgp_kwargs["flux"] = np.repeat(sums, repeat)
 
 
 def sgp_subdivisions(image, psf, bkg, subdiv_shape=(256, 256), overlap=32, betaParams=None,
-                     device_out=False, bkg_box_size=None, bkg_filter_size=(3, 3), **sgp_kwargs):
+                     device_out=False, bkg_box_size=None, bkg_filter_size=(3, 3),
+                     flux_localbkg_width=0, flux_deblend=False, **sgp_kwargs):
     """Field -> overlapping subdivisions -> one batched beta-SGP solve -> mean
     mosaic.  ``bkg``: scalar, or a field-sized map (cut like the image, as the
     application cuts its background map).  ``psf``: one stamp for every tile,
@@ -163,7 +169,10 @@ def sgp_subdivisions(image, psf, bkg, subdiv_shape=(256, 256), overlap=32, betaP
     itself with background.Background2D(image, bkg_box_size, bkg_filter_size).
     ``flux="segments"`` gives every tile the application's flux constraint, the
     sum of ``segment_flux`` of ``segmentation.source_info(tile, bkg_box_size,
-    n_pixels=5)``.
+    n_pixels=5, localbkg_width=flux_localbkg_width, deblend=flux_deblend)``;
+    ``flux_localbkg_width=5, flux_deblend=True`` is the reference's constraint
+    (its catalogue subtracts a local background, utils.py:244-246), the
+    defaults 0 and ``False`` leave the sums as they were.
     Returns (mosaic, footprint, solve outputs); numpy unless device_out."""
     import sgp
     torch = _B.torch
@@ -185,7 +194,8 @@ def sgp_subdivisions(image, psf, bkg, subdiv_shape=(256, 256), overlap=32, betaP
         bk = torch.full((len(boxes),), float(b), dtype=torch.float64, device="cuda")
     if hasattr(psf, "stamps"):  # spatially varying DIAPL model: a stamp per tile centre
         psf = psf.stamps(tile_centres(boxes), normalize=True, device_out=True)
-    _segment_flux(sgp_kwargs, tiles, bkg_box_size)
+    _segment_flux(sgp_kwargs, tiles, bkg_box_size, localbkg_width=flux_localbkg_width,
+                  deblend=flux_deblend)
     out = sgp.sgp_betaDiv_batch(tiles, psf, bk, betaParams=betaParams, device_out=True,
                                 **sgp_kwargs)
     mosaic, foot = coadd_tiles(out["x"], boxes, (H, W))
@@ -199,7 +209,7 @@ def sgp_subdivisions(image, psf, bkg, subdiv_shape=(256, 256), overlap=32, betaP
 
 def sgp_subdivisions_multistart(image, psf, bkg, betas=None, score=None, subdiv_shape=(256, 256),
                                 overlap=32, bkg_box_size=None, bkg_filter_size=(3, 3),
-                                **sgp_kwargs):
+                                flux_localbkg_width=0, flux_deblend=False, **sgp_kwargs):
     """The application's beta search for every subdivision of a field at once
     (application_sgp_subdivisions.py:69-107 per tile): the (tile x candidate)
     product -- n tiles x K initial betas (default: the application's five
@@ -214,8 +224,8 @@ def sgp_subdivisions_multistart(image, psf, bkg, betas=None, score=None, subdiv_
     is the application's photometric score; ``segmentation.flux_fraction_score(
     None, box_size)`` computes it on the device (a score object with a ``batch``
     method gets every candidate in one call); without one the final
-    discrepancy ranks the candidates.  ``flux="segments"`` as in
-    :func:`sgp_subdivisions`.  ``psf``,
+    discrepancy ranks the candidates.  ``flux="segments"``,
+    ``flux_localbkg_width`` and ``flux_deblend`` as in :func:`sgp_subdivisions`.  ``psf``,
     ``bkg`` (``"estimate"`` with ``bkg_box_size`` included) and the keyword
     arguments as in :func:`sgp_subdivisions`.
     Returns (mosaic, footprint, info): info holds the boxes, "betas",
@@ -247,7 +257,8 @@ def sgp_subdivisions_multistart(image, psf, bkg, betas=None, score=None, subdiv_
         pt = psf if torch.is_tensor(psf) else _B.to_dev(np.asarray(psf, dtype=np.float64))
         psf = pt.repeat_interleave(K, dim=0)
     gns = tiles.repeat_interleave(K, dim=0)
-    _segment_flux(sgp_kwargs, tiles, bkg_box_size, repeat=K)
+    _segment_flux(sgp_kwargs, tiles, bkg_box_size, repeat=K, localbkg_width=flux_localbkg_width,
+                  deblend=flux_deblend)
     out = sgp.sgp_betaDiv_batch(gns, psf, bk, betaParams=np.tile(np.asarray(betas, float), n),
                                 **sgp_kwargs)
     t_host = tiles.cpu().numpy()

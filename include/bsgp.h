@@ -405,7 +405,7 @@ int bsgp_solve_resume(bsgp_plan plan, int32_t B, const bsgp_params* params,
 
 /* Source detection, deblending and segment measurement: what
  * utils.source_info (restoration/utils.py:235-247) does with photutils.
- * All four are asynchronous; images of a batch are processed on their own and
+ * All of them are asynchronous; images of a batch are processed on their own and
  * get the bits they get alone; H * W < 2^31 and B <= 65535, else
  * BSGP_ERR_UNSUPPORTED.
  *
@@ -443,6 +443,52 @@ int bsgp_segment_catalog(const double* data, const double* conv, const int32_t* 
                          int32_t H, int32_t W, int32_t cap, const int32_t* nlabels,
                          int32_t* int_cols_out, double* f64_cols_out, int32_t* status_out,
                          void* stream);
+/* The local background of photutils' SourceCatalog(..., localbkg_width=L)
+ * (utils.py:244-246), modelled on photutils and pinned to the catalogue the
+ * reference published for its frame.  For label l with inclusive box x0..x1,
+ * y0..y1 (the int columns of bsgp_segment_catalog), w = x1 - x0 + 1,
+ * h = y1 - y0 + 1 and L = localbkg_width > 0:
+ *  L1 centre cx = (x0 + x1) / 2, cy = (y0 + y1) / 2; inner half-widths 0.75 w
+ *     and 0.75 h; outer half-widths inner + L.
+ *  L2 pixel (x, y) belongs to the annulus if |x - cx| < outer_x and
+ *     |y - cy| < outer_y, not both |x - cx| < inner_x and |y - cy| < inner_y,
+ *     it lies inside the image, and its label is 0 (pixels of any segment are
+ *     left out, not only those of l).  Every comparison is strict.  Its value
+ *     in data must be finite; values are widened to float64.
+ *  L3 fewer than min_pixels (photutils: 10) values give a local background of
+ *     0.0 and BSGP_LOCALBKG_FEW.
+ *  L4 sigma clipping, astropy SigmaClip(sigma, maxiters, cenfunc='median',
+ *     stdfunc='std') as bsgp_background2d does it: the values are sorted once,
+ *     clipping moves the two ends of the sorted range, the bounds median -+
+ *     sigma * std are inclusive, std is the population standard deviation.
+ *     photutils uses sigma = 3, maxiters = 10.
+ *  L5 SExtractor's mode of the survivors from their mean, median and
+ *     population std: std == 0 gives mean; |mean - median| / std < 0.3 gives
+ *     2.5 median - 1.5 mean; anything else gives median.
+ *  L6 with apply != 0, in float64 with one rounding per operation:
+ *     segment_flux -= area * lb, min_value -= lb, max_value -= lb (columns 0,
+ *     1, 2 of f64_cols, rewritten in place).  The other columns are untouched.
+ * data: float32 or float64 (dtype); labels, cap, nlabels, int_cols [B][cap][5]
+ * and f64_cols [B][cap][8] as bsgp_segment_catalog takes and writes them
+ * (f64_cols may be NULL when apply == 0).  lb_out: float64 [B][cap];
+ * npix_out: int32 [B][cap][2] = values gathered, survivors of the clipping.
+ * Rows beyond an image's labels and rows of area 0 get zeros.  An annulus of
+ * more than BSGP_LOCALBKG_MAX values gets lb = 0, no correction and
+ * BSGP_LOCALBKG_OVER_CAP.  status_out [B]: the OR over the image's labels.
+ * Sums run over the sorted values, so a batch gives each image the bits it
+ * gets alone.  B == 0 is a no-op that follows no pointer.  Asynchronous.
+ * BSGP_ERR_ARG: localbkg_width not finite or <= 0, sigma not > 0, maxiters < 0,
+ * min_pixels < 1, cap < 1, B < 0, a NULL array; the shape limits of
+ * bsgp_segment_catalog give BSGP_ERR_UNSUPPORTED. */
+#define BSGP_LOCALBKG_MAX 8192
+#define BSGP_LOCALBKG_FEW 1
+#define BSGP_LOCALBKG_OVER_CAP 2
+int bsgp_segment_local_background(const void* data, int32_t dtype, const int32_t* labels, int32_t B,
+                                  int32_t H, int32_t W, int32_t cap, const int32_t* nlabels,
+                                  const int32_t* int_cols, double* f64_cols,
+                                  double localbkg_width, double sigma, int32_t maxiters,
+                                  int32_t min_pixels, int32_t apply, double* lb_out,
+                                  int32_t* npix_out, int32_t* status_out, void* stream);
 
 /* What SourceFinder(npixels, deblend=True) (utils.py:235, called at :242) adds to
  * detect_sources: photutils' deblend_sources, modelled on its documentation and
