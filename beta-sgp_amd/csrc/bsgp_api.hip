@@ -172,6 +172,11 @@ struct bsgp_plan_s {
   size_t slot_stride = 0;
   size_t vec_stride = 0;
   size_t spec_off = 0;
+  // second half spectrum per image (SolveArgs::spec2): allocated by the first
+  // solve that can speculate, so plans that never do (adaptive beta, float32,
+  // teams, phase kernels) keep their footprint
+  cd* spec2 = nullptr;
+  size_t spec2_slots = 0;
   ImgState* st = nullptr;
   size_t st_n = 0;
   int* active = nullptr;     // device counter of images still iterating
@@ -246,6 +251,21 @@ static int ensure_plist(bsgp_plan p, size_t n) {
     p->plist_n = 0;
     HIP_TRY(hipMalloc(&p->plist, n * sizeof(double)));
     p->plist_n = n;
+  }
+  return BSGP_OK;
+}
+
+static size_t spec2_stride(const bsgp_plan_s* p) {
+  return round_up((size_t)p->g.sld * p->g.Qh, 16);  // the slot spectrum's size
+}
+
+static int ensure_spec2(bsgp_plan p, size_t slots) {
+  if (slots > p->spec2_slots) {
+    if (p->spec2) HIP_TRY(hipFree(p->spec2));
+    p->spec2 = nullptr;
+    p->spec2_slots = 0;
+    HIP_TRY(hipMalloc(&p->spec2, slots * spec2_stride(p) * sizeof(cd)));
+    p->spec2_slots = slots;
   }
   return BSGP_OK;
 }
@@ -679,6 +699,7 @@ int bsgp_plan_destroy(bsgp_plan p) {
   if (p->tw) (void)hipFree(p->tw);
   if (p->tf) (void)hipFree(p->tf);
   if (p->ws) (void)hipFree(p->ws);
+  if (p->spec2) (void)hipFree(p->spec2);
   for (int i = 1; i < p->nsub; ++i) {
     if (p->sub[i]) (void)hipStreamDestroy(p->sub[i]);
     if (p->ev_join[i]) (void)hipEventDestroy(p->ev_join[i]);
@@ -934,6 +955,8 @@ static int solve_impl(bsgp_plan p, int32_t B, const bsgp_params* prm, const bsgp
   a.pw = p->pw;
   a.storage = p->storage;
   a.spec_off = p->spec_off;
+  a.spec2 = nullptr;
+  a.spec2_stride = 0;
   a.spin_limit = (unsigned)env_knob("BSGP_SPIN_LIMIT", 1ll << 26, 0, 0xffffffffll);
   a.ls_predict = (int)env_knob("BSGP_LS_PREDICT", 1, 0, 5);
   a.ls_cap = (prm->beta > 0.0 && prm->beta < 1.0)
@@ -946,9 +969,15 @@ static int solve_impl(bsgp_plan p, int32_t B, const bsgp_params* prm, const bsgp
     rc = ensure_plist(p, (size_t)B * a.plist_stride);
     if (rc) return rc;
     a.plist = p->plist;
-    if (T > 1) {  // teams keep their projection lists in LDS as far as they fit
-      const size_t fit = p->lds_fft_bytes / ((size_t)plan_block(p->g) * 2 * sizeof(double));
+    // the projection lists stay in the transform buffers' LDS as far as they
+    // fit: teams, and one-workgroup images of per-wave plans (there
+    // BSGP_LIST_LDS caps the entries per thread; 0: every entry in global memory)
+    const size_t fit = p->lds_fft_bytes / ((size_t)plan_block(p->g) * 2 * sizeof(double));
+    if (T > 1) {
       a.list_lds = (int)std::min<size_t>((size_t)a.lcap, fit);
+    } else if (!p->g.coop) {
+      const size_t cap = (size_t)env_knob("BSGP_LIST_LDS", 1 << 20, 0, 1 << 20);
+      a.list_lds = (int)std::min<size_t>(std::min<size_t>((size_t)a.lcap, fit), cap);
     }
   }
   hipStream_t s = (hipStream_t)stream;
@@ -975,6 +1004,14 @@ static int solve_impl(bsgp_plan p, int32_t B, const bsgp_params* prm, const bsgp
   const bool persist =
       prm->persistent && T == 1 && !track && (!rs || ring_rule || rs->uniform);
   if (persist) S = 1;
+  // the speculative fused pass of the persistent line search writes w's rows
+  // to a second spectrum per image; without one the kernel never speculates
+  if (persist && persist_speculates(a)) {
+    rc = ensure_spec2(p, (size_t)B);
+    if (rc) return rc;
+    a.spec2 = p->spec2;
+    a.spec2_stride = spec2_stride(p);
+  }
   // the flagship plan's compile-time-geometry phases (k_persist): this solve's
   // choice (bsgp_plan_set_static_geo, else BSGP_STATIC_GEO, default on), taken
   // only when the kernel launched carries them and every plan value they fold

@@ -1991,9 +1991,12 @@ __device__ __forceinline__ void row_inv_fwd(const Geo& G, const Part& D, cd* spe
 // r2c_split), so sums and spectra have the bits of the two separate passes.
 // Both transform buffers are busy until the forward FFT: the next pair's
 // spectrum is gathered through registers, not staged ahead.
+// The rows are read from `src` and written to `dst` (only this wave touches
+// rows r, r + 1 of either, so dst == src updates the spectrum in place); both
+// sides keep the plain row-side policy of POL.
 template <int JCH = kJCH, bool COMP = true, unsigned POL = 0, class LD, class CP, class GT = Geo>
-__device__ __forceinline__ void row_inv_fwd2(const GT& G, const Part& D, cd* spec, cd* lds,
-                                             LD&& ld, CP&& cp) {
+__device__ __forceinline__ void row_inv_fwd2(const GT& G, const Part& D, const cd* src, cd* dst,
+                                             cd* lds, LD&& ld, CP&& cp) {
   using V = decltype(ld(0, 0));
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const bool pair_ok = (G.sld & 1) == 0;
@@ -2002,7 +2005,7 @@ __device__ __forceinline__ void row_inv_fwd2(const GT& G, const Part& D, cd* spe
     cd* b = a + G.lpad;
     for (int r = 2 * (D.gw0 + w); r < G.H; r += 2 * D.gws) {
       const bool two = row_two(G, r, G.H);
-      gather_pair<POL>(G, spec, G.sld, r, two, a, lane);
+      gather_pair<POL>(G, src, G.sld, r, two, a, lane);
       V v0[JCH], v1[JCH];
       load_rows<JCH>(ld, r, two, 0, lane, G.W, v0, v1);
       wave_sync();
@@ -2029,7 +2032,7 @@ __device__ __forceinline__ void row_inv_fwd2(const GT& G, const Part& D, cd* spe
       for (int k = lane; k < G.Qh; k += 64) {
         cd ak, bk;
         r2c_split(Y, G.Q, k, &ak, &bk);
-        store_pair<POL>(spec + (size_t)k * G.sld + r, two, pair_ok, ak, bk);
+        store_pair<POL>(dst + (size_t)k * G.sld + r, two, pair_ok, ak, bk);
       }
       wave_sync();
     }

@@ -30,8 +30,13 @@ struct ImgState {
   int g32;
   // which of the two x_tf / pw buffer pairs is current (slot_bufs): a line
   // search that accepts its speculative fused pass (ls_phase) flips it.  It
-  // fills the padding before gfill: the size of the state does not change.
+  // fills the padding before gfill.
   int par_tf;
+  // this iteration's line search accepted its speculative pass: w's spectrum is
+  // the speculation buffer's (SolveArgs::spec2), not the slot's.  ls_phase
+  // writes it every iteration, bb_phase reads it; nothing carries it across an
+  // iteration boundary (dir_phase always writes the slot's spectrum).
+  int par_spec;
   double gfill;
   double Valpha[32];
   double Fold[32];
@@ -85,7 +90,8 @@ struct SolveArgs {
   double* plist;
   size_t plist_stride;  // doubles per image (both arrays)
   int lcap;             // list capacity per thread (pixels one thread streams)
-  int list_lds;         // teams: list entries per thread kept in the transform buffers' LDS
+  int list_lds;         // list entries per thread kept in the transform buffers' LDS (teams and
+                        // one-workgroup images of per-wave plans; BSGP_LIST_LDS caps the latter)
   PwProg pw;            // numpy float32 sum order over N (params.gn_f32)
   int storage;          // BSGP_STORAGE_F64 / F32 (iteration vectors, Bufs<V>)
   size_t spec_off;      // doubles from a slot's start to its spectrum
@@ -100,6 +106,13 @@ struct SolveArgs {
                         // accepted lam = 1; 2 / 3: always an accept / a stagnation (tests);
                         // 4: as 1, and a stagnation after a tiny step; 5: stagnations only
                         // (both measured slower than 1 on C3).  BSGP_LS_PREDICT
+  // second half spectrum per image for the speculative fused pass (ls_phase:
+  // it reads A(d)'s rows from the slot's spectrum and writes w's rows here, so
+  // a missed speculation finds A(d) intact).  The plan allocates it for solves
+  // that can speculate (persistent, per-wave float64, fixed general beta with
+  // the series, ls_predict != 0); nullptr otherwise: no speculation.
+  cd* spec2;
+  size_t spec2_stride;  // complex values per image
 };
 
 hipError_t launch_setup(const SolveArgs& a, size_t lds, hipStream_t s);
@@ -278,6 +291,8 @@ hipError_t persist_resident_per_cu(const SolveArgs& a, int K, size_t lds, int* p
 // whether the persistent kernel this solve launches has static-geometry phases
 // for the plan's geometry (SolveArgs::static_geo may then be set)
 bool persist_static_geo(const SolveArgs& a, int K);
+// whether a persistent solve can take the speculative fused pass (needs SolveArgs::spec2)
+bool persist_speculates(const SolveArgs& a);
 hipError_t persist_phase_prof(unsigned long long* out, int n, int reset);
 void persist_kernels_all(std::vector<const void*>& f);
 

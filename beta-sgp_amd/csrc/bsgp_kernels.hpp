@@ -59,6 +59,11 @@ constexpr int kLs1Jch = 1;
 #ifndef BSGP_LS1_K2
 #define BSGP_LS1_K2 0
 #endif
+// The unit's persistent solver keeps the projection lists of one-workgroup
+// images in LDS (SolveArgs::list_lds): bsgp_persist.hip only.
+#ifndef BSGP_PERSIST_LL
+#define BSGP_PERSIST_LL 0
+#endif
 // Stream policy of the persistent solver's phases (bsgp_device.hpp, "cache
 // policy": a bitmask of kNt* classes made non-temporal).  Only k_persist's
 // phase functions take it; the phase kernels are always plain.  Each persistent
@@ -214,6 +219,7 @@ struct Bufs {
           // gradient (k_bb) and the next line search's series moments
   V *xtf2, *pw2;  // the other x_tf / pw pair (ImgState::par_tf): free for a speculative accept
   cd* spec;
+  cd* spec2;  // the speculative pass's destination spectrum (SolveArgs::spec2), or nullptr
 };
 
 template <class V>
@@ -239,6 +245,7 @@ __device__ __forceinline__ Bufs<V> slot_bufs(const SolveArgs& A, int img, int pa
   b.pw = par_tf ? sp + v : vb + 6 * v;
   b.pw2 = par_tf ? vb + 6 * v : sp + v;
   b.spec = reinterpret_cast<cd*>(ws + A.spec_off);
+  b.spec2 = A.spec2 ? A.spec2 + (size_t)img * A.spec2_stride : nullptr;
   return b;
 }
 
@@ -692,6 +699,7 @@ __device__ __forceinline__ void setup_phase(const SolveArgs& A, int img) {
     for (int k = 0; k < P.M; ++k) st.Fold[k] = -1e30;
     st.par = 0;
     st.par_tf = 0;
+    st.par_spec = 0;
     st.Xones = P.init_recon == 0;  // X = ones until the first BB update (sgp.py:279-280)
     st.stop = 0;
     st.iter = 1;
@@ -787,8 +795,9 @@ constexpr int kProjWidePx = 16;
 // the transform buffers' LDS, which the row pass after the projection is the
 // next to use (C2 and the application's subdivisions: the whole list, so an
 // evaluation reads no global memory; C4: 16 of up to 32 entries), the rest
-// in global memory (LL: compiled in; the persistent one-workgroup solver
-// keeps global lists).
+// in global memory.  One-workgroup images of per-wave plans do the same (C3:
+// 8 of ~10 entries on average).  LL: compiled in (BSGP_PERSIST_LL for the
+// persistent solver's units: the float64 per-wave one).
 template <class V, bool LL, unsigned POL = 0>
 __device__ __forceinline__ ProjOut cached_projection(const SolveArgs& A, int img, const Part& Pt, Team& tm,
                                      const Dir& D, const Bufs<V>& B, double* red, cd* lds,
@@ -1254,39 +1263,44 @@ __device__ __forceinline__ void ls_phase(const SolveArgs& A, int img) {
   //    fused pass below: the first trial's sums only (no moments, no u =
   //    d_tf / a, no pw operand, no second trial), and the accept's work on the
   //    same registers: x_tf + d_tf and den^(b-1) go to the slot's other
-  //    x_tf / pw pair and the rows of w are transformed in place of A(d)'s.
-  //    If the first trial passes, the pair becomes current (ImgState::par_tf)
-  //    and AT's column pass follows at once; if not, the current pair is
-  //    untouched, ls_replay supplies the moments and the search goes on (its
-  //    accept pass rewrites every row of the spectrum).
+  //    x_tf / pw pair and the rows of w go to the second spectrum (Bufs::spec2;
+  //    d_tf is not stored: an accepted first trial never reads it).
+  //    If the first trial passes, the pair becomes current (ImgState::par_tf),
+  //    AT's column pass follows at once on spec2 and bb_phase reads AT(w) from
+  //    there (ImgState::par_spec); if not, the current pair and A(d)'s spectrum
+  //    are untouched and the ordinary pass 1 below runs as if nothing had been
+  //    predicted: it recomputes the first trial's sums (the same bits, the same
+  //    rejection), stores d_tf and supplies the moments, max|u| and the second
+  //    trial.  That rerun is the repair of a miss, not a counted pass or trial.
   //  * stagnate (the last step was below kLsStagLam): the second trial will
   //    come from the closed form, so its direct sums are skipped.
   // A prediction only selects which route computes the sums.  Where the search
-  // then needs one that was left out, ls_replay below sums it over the stored
-  // (x_tf, d_tf, gn, pw) with pass 1's wave, row and lane assignment: every
-  // value accumulates the same terms in the same order per lane and goes
-  // through the same block reduction (each value's tree is its own), so it has
-  // the bits pass 1 would have produced.
+  // then needs the second trial's sums that a predicted stagnation left out,
+  // ls_replay below sums them over the stored (x_tf, d_tf, gn) with pass 1's
+  // wave, row and lane assignment: every value accumulates the same terms in
+  // the same order per lane and goes through the same block reduction (each
+  // value's tree is its own), so it has the bits pass 1 would have produced.
   constexpr bool kPredBuild = PRED && BSGP_LS1_K2 && !COOP && !ADAPT &&
                               (MODE == 3 || MODE == 4) && sizeof(V) == 8;
   constexpr double kLsStagLam = 1e-4;  // (tools/ls_predict_replay.py)
   int pred = 0;                        // 0: none (the full pass 1), 1: accept, 2: stagnate
   if constexpr (kPredBuild) {
-    if (series && tm.T == 1 && A.ls_predict != 0) {
+    if (series && tm.T == 1 && A.ls_predict != 0 && B.spec2 != nullptr) {
       const double ll = st.lam;
       const int lp = A.ls_predict;
       pred = lp == 2 ? 1 : lp == 3 ? 2 : ll == 1.0 ? (lp == 5 ? 0 : 1) : ll < kLsStagLam ? (lp >= 4 ? 2 : 0) : 0;
     }
   }
-  const bool k2 = BSGP_LS1_K2 && !COOP && series && pred == 0;
+  // (a predicted accept that misses reruns pass 1 with the second trial)
+  const bool k2 = BSGP_LS1_K2 && !COOP && series && pred != 2;
   const double lam2 = lam * P.beta;
   double f2 = NAN;     // the second trial's objective from pass 1
   bool have2 = false;  // f2 holds the next trial's objective
   constexpr int O2 = 4 + 2 * (MS + 1);
   constexpr int N1 = O2 + ((BSGP_LS1_K2 && !COOP) ? 2 : 0);  // lam=1 sums, const, dDiv/dbeta, P_m, Q_m, lam=beta sums
-  // The sums a prediction left out of pass 1 (with_mom: the moments and max|u|
-  // as well as the second trial's sums); not a pass of ls_passes.
-  auto ls_replay = [&](bool with_mom) __attribute__((always_inline)) {
+  // The second trial's sums that a predicted stagnation left out of pass 1;
+  // not a pass of ls_passes.
+  auto ls_replay = [&]() __attribute__((always_inline)) {
     if constexpr (kPredBuild) {
       PH_T(tr0);
       double t1[N1];
@@ -1304,21 +1318,6 @@ __device__ __forceinline__ void ls_phase(const SolveArgs& A, int img) {
               const double v = ldp<kO8>(B.dtf + i);  // float64 storage: the value pass 1 had in registers
               const double g = gdec(g_raw<kO8>(g32, B.gns, i));
               const double bkv = opt_ld<kO8>(bmap, B.bks, i, bks_scalar);
-              if (with_mom) {
-                const double a = x0 + bkv;
-                const double u = v / a;
-                const double p0 = ldp<kO8>(B.pw + i);
-                const double A0 = a * p0, B0 = (MODE == 4 ? (double)(obj.c2f * (float)g) : g) * p0;
-                double um = 1.0;
-#pragma unroll
-                for (int m = 0; m <= MS; ++m) {
-                  t1[4 + m] += A0 * um;
-                  t1[4 + MS + 1 + m] += B0 * um;
-                  um *= u;
-                }
-                const double au = fabs(u);
-                umax = (au > umax || au != au || !(a > 0)) ? (a > 0 ? au : INFINITY) : umax;
-              }
               const double x2 = x0 + lam2 * v;
               obj.template terms_m<MODE>(x2, x2 + bkv, g, &t1[O2]);
             }
@@ -1326,21 +1325,13 @@ __device__ __forceinline__ void ls_phase(const SolveArgs& A, int img) {
         }
       }
       team_sum_max<N1>(t1, umax, red, tm);
-      if (with_mom) {
-        rho = umax;
-        if (threadIdx.x == 0) {
-          for (int m = 0; m <= MS; ++m) {
-            ser[m] = t1[4 + m];
-            ser[MS + 1 + m] = t1[4 + MS + 1 + m];
-          }
-        }
-      }
       f2 = obj.combine(konst, t1[O2], t1[O2 + 1], flux, (double)N);
       have2 = true;
       PH_ADD(34, tr0);
     }
   };
   bool spec_acc = false;  // the speculative pass was accepted: no accept pass
+  bool spec_miss = false;  // it was rejected: pass 1 runs after all
   if constexpr (kPredBuild) {
     if (pred == 1) {
       double ts[2] = {0.0, 0.0};
@@ -1351,7 +1342,7 @@ __device__ __forceinline__ void ls_phase(const SolveArgs& A, int img) {
         double x0, g, bkv;
       };
       row_inv_fwd2<kLs1Jch, kLsComp, POL>(
-          G, Pt, B.spec, lds,
+          G, Pt, B.spec, B.spec2, lds,
           [&](int r, int j) {
             const int i = r * G.W + j;
             SpIn q;
@@ -1362,7 +1353,6 @@ __device__ __forceinline__ void ls_phase(const SolveArgs& A, int img) {
           },
           [&](int r, int j, double v, const SpIn& q) {
             const int i = r * G.W + j;
-            stp<kW>(B.dtf + i, (V)v);
             const double g = gdec(q.g);
             const double xt = q.x0 + lam * v;
             const double den = xt + q.bkv;
@@ -1383,12 +1373,15 @@ __device__ __forceinline__ void ls_phase(const SolveArgs& A, int img) {
         accepted = true;
         spec_acc = true;
       } else {
-        lam = lam * P.beta;
+        spec_miss = true;  // lam stays the first trial's: pass 1 rejects it again
       }
     }
   }
   // ---- pass 1, fused into the inverse rows that produce d_tf: lam = 1 direct
-  if (pred != 1) {
+  // (also the repair of a missed speculation: A(d)'s spectrum is intact, the
+  // pass and its trial were counted above)
+  if (pred != 1 || spec_miss) {
+    PH_T(tp1);
     double t1[N1];
 #pragma unroll
     for (int k = 0; k < N1; ++k) t1[k] = 0.0;
@@ -1449,7 +1442,11 @@ __device__ __forceinline__ void ls_phase(const SolveArgs& A, int img) {
     } else {
       team_sum<N1>(t1, red, tm);
     }
-    PH_ADD(4, tk0);
+    if (spec_miss) {
+      PH_ADD(34, tp1);
+    } else {
+      PH_ADD(4, tk0);
+    }
     if (series && threadIdx.x == 0) {
       for (int m = 0; m <= MS; ++m) {
         ser[m] = t1[4 + m];
@@ -1457,8 +1454,10 @@ __device__ __forceinline__ void ls_phase(const SolveArgs& A, int img) {
       }
     }
     if (adapt) konst = k32 ? konst32(obj.beta) : t1[2];
-    ++passes;
-    ++nls;
+    if (!spec_miss) {
+      ++passes;
+      ++nls;
+    }
     const double f1 = obj.combine(konst, t1[0], t1[1], flux, (double)N);
     if (f1 <= fr + P.gamma * lam * gd || lam < 1e-12) {
       f_acc = f1;
@@ -1480,15 +1479,9 @@ __device__ __forceinline__ void ls_phase(const SolveArgs& A, int img) {
 #ifdef BSGP_PHASE_PROF
   // (prediction counters: iterations per prediction, then those it missed)
   if (threadIdx.x == 0 && pred) atomicAdd(&g_phase[pred == 1 ? 32 : 33], 1ull);
+  // (a predicted accept whose first trial failed: pass 1 ran as its repair)
+  if (threadIdx.x == 0 && spec_miss) atomicAdd(&g_phase[35], 1ull);
 #endif
-  // a predicted accept whose first trial failed: the moments, max|u| and the
-  // second trial's sums after all
-  if (pred == 1 && !accepted) {
-    ls_replay(true);
-#ifdef BSGP_PHASE_PROF
-    if (threadIdx.x == 0) atomicAdd(&g_phase[35], 1ull);
-#endif
-  }
   const bool have_mom = !spec_acc;  // ser[] holds this iteration's moments
   // binomial coefficients of the series (and, for the tail bound, the
   // scaled leading terms |binom(., MS+1)| P_MS / P_0 of both series)
@@ -1524,7 +1517,7 @@ __device__ __forceinline__ void ls_phase(const SolveArgs& A, int img) {
   PH_T(tk1);
   // a predicted stagnation whose second trial is outside the closed form
   if (pred == 2 && !accepted && !series_ok(lam)) {
-    ls_replay(false);
+    ls_replay();
 #ifdef BSGP_PHASE_PROF
     if (threadIdx.x == 0) atomicAdd(&g_phase[36], 1ull);
 #endif
@@ -1725,7 +1718,7 @@ __device__ __forceinline__ void ls_phase(const SolveArgs& A, int img) {
   if (A.fuse_col & 2) {  // AT's column pass follows here
     PH_T(tc0);
     team_sync(tm);
-    col_conv<COOP, POL>(G, Pt, B.spec, tf_of(G, img, 1), lds);
+    col_conv<COOP, POL>(G, Pt, spec_acc ? B.spec2 : B.spec, tf_of(G, img, 1), lds);
     PH_ADD(3, tc0);
   }
   PH_ADD(7, tk0);
@@ -1741,6 +1734,7 @@ __device__ __forceinline__ void ls_phase(const SolveArgs& A, int img) {
     st.konst = konst;
     st.lam = lam_acc;
     if (spec_acc) st.par_tf ^= 1;
+    st.par_spec = spec_acc ? 1 : 0;
     st.E_ls += nls;
     st.ls_passes += passes;
     st.ls_series += series_evals;
@@ -1761,7 +1755,9 @@ __global__ void __launch_bounds__(kBlock) BSGP_LS_ATTR k_ls(SolveArgs A) {
 // sgp.py:337-414 (= 785-879): g_new = g1(den) - AT(w), x += lam*d, the
 // Barzilai-Borwein step lengths with the tau alternation, the stop rules,
 // and the outputs once the image stops (sgp.py:424-438).
-template <bool COOP, class V, unsigned POL = 0, class GT = Geo>
+// SP2: the build's line search can leave AT(w) in the second spectrum
+// (ImgState::par_spec; the persistent per-wave float64 solver).
+template <bool COOP, class V, unsigned POL = 0, class GT = Geo, bool SP2 = false>
 __device__ __forceinline__ void bb_phase(const SolveArgs& A, int img) {
   constexpr bool kO16 = (POL & kNtO16) != 0, kO8 = (POL & kNtO8) != 0, kW = (POL & kNtW) != 0;
   BSGP_LDS_VIEWS_G(A, GT);
@@ -1789,11 +1785,15 @@ __device__ __forceinline__ void bb_phase(const SolveArgs& A, int img) {
   const double fv = st.fv, Dcoeff = st.Dcoeff, tol = st.tol, fold_last = st.Fold[P.M - 1];
   const double sc = st.sc;
   double bb[6] = {0, 0, 0, 0, 0, 0};  // bk, ck, sk2.sk2, yk2.yk2, sk.sk, x.x
+  const cd* spec_w = B.spec;  // AT(w), left by the line search
+  if constexpr (SP2) {
+    if (st.par_spec) spec_w = B.spec2;
+  }
   struct BbIn {
     double p, x, g;
   };
   row_inv2<BSGP_BB_PRE, kBbJch, kBbComp, COOP, BSGP_BB_PIPE, 19, POL>(
-      G, Pt, B.spec, lds,
+      G, Pt, spec_w, lds,
       [&](int r, int j) {
         const int i = r * G.W + j;
         BbIn q;
@@ -2000,7 +2000,8 @@ __device__ __attribute__((noinline)) void persist_setup(ArgRef r, int img) {
 }
 template <bool COOP, class V, unsigned POL, class GT = Geo>
 __device__ __attribute__((noinline)) void persist_dir(ArgRef r, int img) {
-  dir_phase<COOP, V, false, POL, GT>(args_of(r), __builtin_amdgcn_readfirstlane(img));
+  dir_phase<COOP, V, (BSGP_PERSIST_LL) != 0, POL, GT>(args_of(r),
+                                                    __builtin_amdgcn_readfirstlane(img));
 }
 template <bool COOP, unsigned POL, class GT = Geo>
 __device__ __attribute__((noinline)) void persist_col_a(ArgRef r, int img) {
@@ -2024,7 +2025,8 @@ __device__ __attribute__((noinline)) void persist_ls(ArgRef r, int img) {
 }
 template <bool COOP, class V, unsigned POL, class GT = Geo>
 __device__ __attribute__((noinline)) void persist_bb(ArgRef r, int img) {
-  bb_phase<COOP, V, POL, GT>(args_of(r), __builtin_amdgcn_readfirstlane(img));
+  constexpr bool kSp2 = BSGP_LS1_K2 && !COOP && std::is_same<V, double>::value;
+  bb_phase<COOP, V, POL, GT, kSp2>(args_of(r), __builtin_amdgcn_readfirstlane(img));
 }
 
 // Slot order (fixed-length solves, stop rules 0/1): task t = (k - 1) * nimg + i

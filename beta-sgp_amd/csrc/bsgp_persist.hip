@@ -29,6 +29,11 @@
 #ifndef BSGP_STATIC_GEO
 #define BSGP_STATIC_GEO 1
 #endif
+// one-workgroup images keep their projection lists in the transform buffers'
+// LDS as far as they fit (cached_projection, SolveArgs::list_lds)
+#ifndef BSGP_PERSIST_LL
+#define BSGP_PERSIST_LL 1
+#endif
 #include "bsgp_kernels.hpp"
 
 namespace bsgp {
@@ -55,6 +60,17 @@ bool persist_static_geo(const SolveArgs& a, int K) {
   const int mode = ls_mode(a, &adapt);
   return static_geo_kernel<double, (BSGP_STATIC_GEO != 0)>(false, K >= 2 ? 2 : K, mode, adapt) &&
          static_geo_plan(a);
+}
+
+// The kernel the solve takes carries the line search's outcome prediction and
+// the solve's parameters let it speculate (ls_phase's kPredBuild and `pred`):
+// such a solve needs the second spectrum (SolveArgs::spec2).
+bool persist_speculates(const SolveArgs& a) {
+  if (a.g.coop || app_static_plan(a.g, a.storage) || a.storage != BSGP_STORAGE_F64) return false;
+  bool adapt = false;
+  const int mode = ls_mode(a, &adapt);
+  return (BSGP_LS1_K2) != 0 && !adapt && (mode == 3 || mode == 4) && a.prm.ls_series != 0 &&
+         a.T == 1 && a.ls_predict != 0;
 }
 
 // Workgroups of the persistent kernel a solve would launch that one CU holds.

@@ -300,6 +300,7 @@ __global__ void __launch_bounds__(kStBlock) k_state_load(StateArgs S) {
   }
   st.par = 0;
   st.par_tf = 0;  // the record's x_tf / pw went to the first pair
+  st.par_spec = 0;
   st.Xones = h->Xones;
   st.stop = fin != 0;
   st.iter = done + 1;

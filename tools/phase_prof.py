@@ -31,11 +31,11 @@ SLOTS = {0: "k_dir projection", 1: "k_dir row pass", 2: "k_dir total", 3: "k_col
          25: "  coop rows: spectrum gathers", 26: "  coop rows: FFTs", 27: "  coop rows: operands",
          28: "  coop rows: spectrum stores", 29: "  coop cols: loads", 30: "  coop cols: FFT+TF+store",
          31: "persistent: dequeue + wait for the previous iteration",
-         34: "k_ls replay of skipped sums", 37: "k_ls speculative fused pass",
+         34: "k_ls miss repair (pass 1 rerun / replay)", 37: "k_ls speculative fused pass",
          38: "  ls1 team reduction: own waves", 39: "  ls1 team reduction: other members"}
 # line-search prediction counters (events, not cycles): iterations per
 # prediction and the mispredicted ones among them (a replay pass each)
-COUNTS = {32: "predicted accept", 35: "  first trial failed (replay)",
+COUNTS = {32: "predicted accept", 35: "  first trial failed (pass 1 rerun)",
           33: "predicted stagnation", 36: "  second trial needed (replay)"}
 
 
