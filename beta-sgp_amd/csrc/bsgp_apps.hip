@@ -1,0 +1,431 @@
+// bsgp_apps.hip — the entry points of the C-ABI host layer that take no plan
+// (declared in include/bsgp.h): the projection, tiles, FITS pixels, PSF stamps,
+// sky background, convolution, detection, catalogue, local background,
+// deblending, star-stamp metrics and the divergences.  Each validates its
+// arguments and launches its kernels.
+#include <cmath>
+#include <cstdio>
+#include <string>
+
+#include "bsgp_host.hpp"
+#include "bsgp_psf.hpp"
+
+using namespace bsgp;
+
+extern "C" {
+
+int bsgp_project_df(int64_t n, double b, const double* c, const double* dia, double scaling,
+                    int32_t has_sat, double ccd_sat_level, double lambda0, double dlambda0,
+                    double tol_lam, int32_t biter, int32_t siter, int32_t max_projs, double* x,
+                    double* info, void* stream) {
+  if (n < 1 || n > 0x7fffffff || !c || !dia || !x || !info)
+    return fail(BSGP_ERR_ARG, "bad arguments");
+  ProjClip clip{has_sat != 0, ccd_sat_level / scaling - 2.220446049250313e-16};
+  HIP_TRY(launch_project_df((int)n, b, c, dia, clip, lambda0, dlambda0, tol_lam, biter, siter,
+                            max_projs, x, info, (hipStream_t)stream));
+  return BSGP_OK;
+}
+
+int bsgp_extract_tiles(const double* img, int32_t H, int32_t W, const int32_t* boxes, int32_t n,
+                       int32_t th, int32_t tw, double* out, void* stream) {
+  if (!img || !boxes || !out || H < 1 || W < 1 || n < 1 || th < 1 || tw < 1 || th > H || tw > W)
+    return fail(BSGP_ERR_ARG, "bad arguments");
+  if ((int64_t)n * th > 0x7fffffff) return fail(BSGP_ERR_ARG, "too many tile rows");
+  HIP_TRY(launch_extract_tiles(img, W, boxes, n, th, tw, out, (hipStream_t)stream));
+  return BSGP_OK;
+}
+
+int bsgp_coadd_tiles(const double* tiles, int32_t n, int32_t th, int32_t tw, const int32_t* boxes,
+                     int32_t H, int32_t W, double* mean, double* footprint, void* stream) {
+  if (!tiles || !boxes || !mean || H < 1 || W < 1 || n < 1 || n > 8192 || th < 1 || tw < 1)
+    return fail(BSGP_ERR_ARG, "bad arguments");
+  HIP_TRY(launch_coadd_tiles(tiles, n, th, tw, boxes, H, W, mean, footprint, (hipStream_t)stream));
+  return BSGP_OK;
+}
+
+int bsgp_fits_to_f64(const void* raw, int64_t n, int32_t bitpix, double bscale, double bzero,
+                     double* out, void* stream) {
+  if (!raw || !out || n < 0) return fail(BSGP_ERR_ARG, "bad arguments");
+  if (bitpix != 8 && bitpix != 16 && bitpix != 32 && bitpix != 64 && bitpix != -32 &&
+      bitpix != -64)
+    return fail(BSGP_ERR_ARG, "BITPIX must be 8, 16, 32, 64, -32 or -64");
+  if (n == 0) return BSGP_OK;
+  HIP_TRY(launch_fits_to_f64(raw, n, bitpix, bscale, bzero, out, (hipStream_t)stream));
+  return BSGP_OK;
+}
+
+int bsgp_psf_stamps(const bsgp_psf_model* m, const double* xy, int32_t n, int32_t spatial,
+                    int32_t normalize, double* out, void* stream) {
+  if (!m || !out || n < 0 || (spatial && !xy) || !m->coeffs)
+    return fail(BSGP_ERR_ARG, "bad arguments");
+  if (m->hw < 0 || m->hw > 255 || m->ngauss < 1 || m->ldeg < 0 || m->sdeg < 0)
+    return fail(BSGP_ERR_ARG, "bad PSF model degrees or half width");
+  PsfModel M{};
+  M.ncomp = m->ngauss * (m->ldeg + 1) * (m->ldeg + 2) / 2;
+  const int nterm = (m->sdeg + 1) * (m->sdeg + 2) / 2;
+  const int need = spatial ? M.ncomp * nterm : M.ncomp;
+  if (M.ncomp > kPsfMaxLocal || need > kPsfMaxCoef)
+    return fail(BSGP_ERR_ARG, "PSF model has too many coefficients");
+  if (m->ncoef < need) return fail(BSGP_ERR_ARG, "too few PSF coefficients for the degrees");
+  if (n == 0) return BSGP_OK;
+  M.cosv = m->cos;
+  M.sinv = m->sin;
+  M.ax = m->ax;
+  M.ay = m->ay;
+  M.sig2 = m->sigma_inc * m->sigma_inc;
+  M.x_orig = m->x_orig;
+  M.y_orig = m->y_orig;
+  M.ngauss = m->ngauss;
+  M.ldeg = m->ldeg;
+  M.sdeg = m->sdeg;
+  M.hw = m->hw;
+  M.ncoef = need;
+  for (int i = 0; i < need; ++i) M.coef[i] = m->coeffs[i];
+  HIP_TRY(launch_psf_stamps(M, xy, n, spatial ? 1 : 0, normalize ? 1 : 0, out,
+                            (hipStream_t)stream));
+  return BSGP_OK;
+}
+
+int bsgp_background2d(const void* data, int32_t dtype, int32_t B, int32_t H, int32_t W, int32_t bh,
+                      int32_t bw, int32_t fh, int32_t fw, double sigma, int32_t maxiters,
+                      double exclude_percentile, int32_t clip, const uint8_t* mask, double* bkg_out,
+                      double* rms_out, double* mesh_out, double* rms_mesh_out, double* medians_out,
+                      int32_t* status_out, void* stream) {
+  if (!data) return fail(BSGP_ERR_ARG, "data is NULL");
+  if (dtype != BSGP_DTYPE_F32 && dtype != BSGP_DTYPE_F64)
+    return fail(BSGP_ERR_ARG, "dtype must be BSGP_DTYPE_F32 or BSGP_DTYPE_F64");
+  if (B < 1 || H < 1 || W < 1) return fail(BSGP_ERR_ARG, "B, H and W must be >= 1");
+  if (bh < 1 || bw < 1) return fail(BSGP_ERR_ARG, "box size (bh, bw) must be >= 1");
+  if (fh < 1 || fw < 1 || fh % 2 == 0 || fw % 2 == 0)
+    return fail(BSGP_ERR_ARG, "filter size (fh, fw) must be odd and >= 1");
+  if (!(sigma >= 0.0)) return fail(BSGP_ERR_ARG, "sigma must be >= 0");
+  if (maxiters < 0) return fail(BSGP_ERR_ARG, "maxiters must be >= 0");
+  if (!(exclude_percentile >= 0.0 && exclude_percentile <= 100.0))
+    return fail(BSGP_ERR_ARG, "exclude_percentile must be in [0, 100]");
+  char msg[192];
+  if ((int64_t)bh * bw > kBkgMaxBox) {
+    snprintf(msg, sizeof msg, "box of %lld pixels: a box holds at most %d (bh * bw <= %d)",
+             (long long)bh * bw, kBkgMaxBox, kBkgMaxBox);
+    return fail(BSGP_ERR_UNSUPPORTED, msg);
+  }
+  if (fh > kBkgMaxFilter || fw > kBkgMaxFilter) {
+    snprintf(msg, sizeof msg, "filter window larger than %d x %d", kBkgMaxFilter, kBkgMaxFilter);
+    return fail(BSGP_ERR_UNSUPPORTED, msg);
+  }
+  const int64_t ny = (H + (int64_t)bh - 1) / bh, nx = (W + (int64_t)bw - 1) / bw;
+  if (ny * nx > kBkgMaxCells) {
+    snprintf(msg, sizeof msg, "mesh of %lld cells: an image's mesh holds at most %d",
+             (long long)(ny * nx), kBkgMaxCells);
+    return fail(BSGP_ERR_UNSUPPORTED, msg);
+  }
+  if (B > 65535 || H > 65535)
+    return fail(BSGP_ERR_UNSUPPORTED, "B and H must be at most 65535");
+  const size_t ncell = (size_t)(ny * nx);
+  BkgArgs a{};
+  a.data = data;
+  a.mask = mask;
+  a.B = B, a.H = H, a.W = W, a.bh = bh, a.bw = bw, a.fh = fh, a.fw = fw;
+  a.ny = (int)ny, a.nx = (int)nx, a.maxiters = maxiters, a.clip = clip ? 1 : 0;
+  a.sigma = sigma;
+  a.excl_count = exclude_percentile / 100.0 * (double)(bh * bw);
+  a.ws_stride = 6 * ncell + 8;
+  a.bkg = bkg_out, a.rms = rms_out, a.mesh = mesh_out, a.rms_mesh = rms_mesh_out;
+  a.medians = medians_out, a.status = status_out;
+  hipStream_t s = (hipStream_t)stream;
+  // stream-ordered workspace: the call stays asynchronous
+  const size_t wsb = (size_t)B * a.ws_stride * sizeof(double);
+  const size_t wib = (size_t)B * (1 + 3 * ncell) * sizeof(int);
+  void* w = nullptr;
+  HIP_TRY(hipMallocAsync(&w, wsb + wib, s));
+  a.ws = static_cast<double*>(w);
+  a.wsi = reinterpret_cast<int*>(static_cast<char*>(w) + wsb);
+  hipError_t e = launch_bkg_boxstats(a, dtype == BSGP_DTYPE_F32, s);
+  if (e == hipSuccess) e = launch_bkg_mesh(a, s);
+  if (e == hipSuccess && (bkg_out || rms_out)) e = launch_bkg_zoom(a, s);
+  const hipError_t ef = hipFreeAsync(w, s);
+  if (e != hipSuccess) return fail(BSGP_ERR_HIP, std::string("background launch: ") + hipGetErrorString(e));
+  HIP_TRY(ef);
+  return BSGP_OK;
+}
+
+namespace {
+// shape checks shared by the segmentation entry points
+int seg_shape(int32_t B, int32_t H, int32_t W) {
+  if (B < 1 || H < 1 || W < 1) return fail(BSGP_ERR_ARG, "B, H and W must be >= 1");
+  if ((int64_t)H * W > 0x7fffffffLL)
+    return fail(BSGP_ERR_UNSUPPORTED, "an image holds fewer than 2^31 pixels (H * W < 2^31)");
+  if (B > 65535) return fail(BSGP_ERR_UNSUPPORTED, "B must be at most 65535");
+  return BSGP_OK;
+}
+}  // namespace
+
+int bsgp_convolve2d(const void* data, int32_t dtype, int32_t B, int32_t H, int32_t W,
+                    const double* kernel, int32_t kh, int32_t kw, double* out, void* stream) {
+  if (!data) return fail(BSGP_ERR_ARG, "data is NULL");
+  if (!kernel) return fail(BSGP_ERR_ARG, "kernel is NULL");
+  if (!out) return fail(BSGP_ERR_ARG, "out is NULL");
+  if (dtype != BSGP_DTYPE_F32 && dtype != BSGP_DTYPE_F64)
+    return fail(BSGP_ERR_ARG, "dtype must be BSGP_DTYPE_F32 or BSGP_DTYPE_F64");
+  if (kh < 1 || kw < 1) return fail(BSGP_ERR_ARG, "kernel size (kh, kw) must be >= 1");
+  if (int rc = seg_shape(B, H, W)) return rc;
+  if (kh % 2 == 0 || kw % 2 == 0 || kh > kSegMaxKernel || kw > kSegMaxKernel) {
+    char msg[128];
+    snprintf(msg, sizeof msg, "kernel of %d x %d: kernels are odd and at most %d x %d", kh, kw,
+             kSegMaxKernel, kSegMaxKernel);
+    return fail(BSGP_ERR_UNSUPPORTED, msg);
+  }
+  if (H > 65535) return fail(BSGP_ERR_UNSUPPORTED, "H must be at most 65535");
+  SegConvArgs a{};
+  a.data = data, a.kernel = kernel, a.out = out;
+  a.B = B, a.H = H, a.W = W, a.kh = kh, a.kw = kw;
+  HIP_TRY(launch_seg_convolve(a, dtype == BSGP_DTYPE_F32, (hipStream_t)stream));
+  return BSGP_OK;
+}
+
+int bsgp_detect_sources(const void* data, int32_t dtype, int32_t B, int32_t H, int32_t W,
+                        const double* threshold_map, double threshold, int32_t npixels,
+                        int32_t connectivity, const uint8_t* mask, int32_t* labels_out,
+                        int32_t* nlabels_out, void* stream) {
+  if (!data) return fail(BSGP_ERR_ARG, "data is NULL");
+  if (!labels_out || !nlabels_out) return fail(BSGP_ERR_ARG, "labels_out / nlabels_out is NULL");
+  if (dtype != BSGP_DTYPE_F32 && dtype != BSGP_DTYPE_F64)
+    return fail(BSGP_ERR_ARG, "dtype must be BSGP_DTYPE_F32 or BSGP_DTYPE_F64");
+  if (npixels < 1) return fail(BSGP_ERR_ARG, "npixels must be >= 1");
+  if (connectivity != 4 && connectivity != 8)
+    return fail(BSGP_ERR_ARG, "connectivity must be 4 or 8");
+  if (int rc = seg_shape(B, H, W)) return rc;
+  const size_t hw = (size_t)H * W;
+  SegArgs a{};
+  a.data = data, a.thr_map = threshold_map, a.mask = mask, a.thr = threshold;
+  a.B = B, a.H = H, a.W = W, a.npixels = npixels, a.conn = connectivity;
+  a.nblk = (int)((hw + kSegChunk - 1) / kSegChunk);
+  a.labels_out = labels_out, a.nlabels_out = nlabels_out;
+  hipStream_t s = (hipStream_t)stream;
+  // stream-ordered workspace: the call stays asynchronous
+  const size_t per = 2 * hw + (size_t)a.nblk;
+  void* w = nullptr;
+  HIP_TRY(hipMallocAsync(&w, (size_t)B * per * sizeof(int), s));
+  a.lab = static_cast<int*>(w);
+  a.area = a.lab + (size_t)B * hw;
+  a.blk = a.area + (size_t)B * hw;
+  const hipError_t e = launch_seg_detect(a, dtype == BSGP_DTYPE_F32, s);
+  const hipError_t ef = hipFreeAsync(w, s);
+  if (e != hipSuccess) return fail(BSGP_ERR_HIP, std::string("detection launch: ") + hipGetErrorString(e));
+  HIP_TRY(ef);
+  return BSGP_OK;
+}
+
+int bsgp_segment_catalog(const double* data, const double* conv, const int32_t* labels, int32_t B,
+                         int32_t H, int32_t W, int32_t cap, const int32_t* nlabels,
+                         int32_t* int_cols_out, double* f64_cols_out, int32_t* status_out,
+                         void* stream) {
+  if (!data) return fail(BSGP_ERR_ARG, "data is NULL");
+  if (!labels) return fail(BSGP_ERR_ARG, "labels is NULL");
+  if (!int_cols_out || !f64_cols_out || !status_out)
+    return fail(BSGP_ERR_ARG, "int_cols_out / f64_cols_out / status_out is NULL");
+  if (cap < 1) return fail(BSGP_ERR_ARG, "cap must be >= 1");
+  if (int rc = seg_shape(B, H, W)) return rc;
+  SegCatArgs a{};
+  a.data = data, a.conv = conv, a.labels = labels, a.nlabels = nlabels;
+  a.B = B, a.H = H, a.W = W, a.cap = cap;
+  a.icols = int_cols_out, a.fcols = f64_cols_out, a.status = status_out;
+  HIP_TRY(launch_seg_catalog(a, (hipStream_t)stream));
+  return BSGP_OK;
+}
+
+int bsgp_segment_local_background(const void* data, int32_t dtype, const int32_t* labels, int32_t B,
+                                  int32_t H, int32_t W, int32_t cap, const int32_t* nlabels,
+                                  const int32_t* int_cols, double* f64_cols,
+                                  double localbkg_width, double sigma, int32_t maxiters,
+                                  int32_t min_pixels, int32_t apply, double* lb_out,
+                                  int32_t* npix_out, int32_t* status_out, void* stream) {
+  if (!(localbkg_width > 0.0) || !std::isfinite(localbkg_width))
+    return fail(BSGP_ERR_ARG, "localbkg_width must be finite and > 0");
+  if (!(sigma > 0.0)) return fail(BSGP_ERR_ARG, "sigma must be > 0");
+  if (maxiters < 0) return fail(BSGP_ERR_ARG, "maxiters must be >= 0");
+  if (min_pixels < 1) return fail(BSGP_ERR_ARG, "min_pixels must be >= 1");
+  if (dtype != BSGP_DTYPE_F32 && dtype != BSGP_DTYPE_F64)
+    return fail(BSGP_ERR_ARG, "dtype must be BSGP_DTYPE_F32 or BSGP_DTYPE_F64");
+  if (cap < 1) return fail(BSGP_ERR_ARG, "cap must be >= 1");
+  if (B == 0) return BSGP_OK;  // no image: nothing to do, no pointer is followed
+  if (!data) return fail(BSGP_ERR_ARG, "data is NULL");
+  if (!labels || !int_cols) return fail(BSGP_ERR_ARG, "labels / int_cols is NULL");
+  if (apply && !f64_cols) return fail(BSGP_ERR_ARG, "f64_cols is NULL (apply != 0)");
+  if (!lb_out || !npix_out || !status_out)
+    return fail(BSGP_ERR_ARG, "lb_out / npix_out / status_out is NULL");
+  if (int rc = seg_shape(B, H, W)) return rc;
+  LocalBkgArgs a{};
+  a.data = data, a.labels = labels, a.nlabels = nlabels, a.icols = int_cols, a.fcols = f64_cols;
+  a.B = B, a.H = H, a.W = W, a.cap = cap, a.maxiters = maxiters, a.min_pixels = min_pixels;
+  a.apply = apply ? 1 : 0, a.width = localbkg_width, a.sigma = sigma;
+  a.lb = lb_out, a.npix = npix_out, a.status = status_out;
+  hipStream_t s = (hipStream_t)stream;
+  const size_t rows = (size_t)B * cap;
+  HIP_TRY(hipMemsetAsync(lb_out, 0, rows * sizeof(double), s));
+  HIP_TRY(hipMemsetAsync(npix_out, 0, 2 * rows * sizeof(int), s));
+  HIP_TRY(hipMemsetAsync(status_out, 0, (size_t)B * sizeof(int), s));
+  HIP_TRY(launch_localbkg(a, dtype == BSGP_DTYPE_F32, s));
+  return BSGP_OK;
+}
+
+// both deblending entry points; lds_max_box < 0: bsgp_deblend_sources (no global-memory path)
+static int deblend_sources(const double* data, const int32_t* labels, int32_t B, int32_t H, int32_t W,
+                           int32_t cap, const int32_t* nlabels, const int32_t* int_cols,
+                           const uint8_t* select, int32_t npixels, int32_t nlevels, double contrast,
+                           int32_t mode, int32_t connectivity, int32_t lds_max_box,
+                           int32_t* labels_out, int32_t* nlabels_out, int32_t* status_out,
+                           void* stream) {
+  if (!data) return fail(BSGP_ERR_ARG, "data is NULL");
+  if (!labels || !nlabels || !int_cols) return fail(BSGP_ERR_ARG, "labels / nlabels / int_cols is NULL");
+  if (!labels_out || !nlabels_out || !status_out)
+    return fail(BSGP_ERR_ARG, "labels_out / nlabels_out / status_out is NULL");
+  if (labels_out == labels) return fail(BSGP_ERR_ARG, "labels_out must not be labels");
+  if (cap < 1) return fail(BSGP_ERR_ARG, "cap must be >= 1");
+  if (npixels < 1) return fail(BSGP_ERR_ARG, "npixels must be >= 1");
+  if (nlevels < 1) return fail(BSGP_ERR_ARG, "nlevels must be >= 1");
+  if (!(contrast >= 0.0 && contrast <= 1.0)) return fail(BSGP_ERR_ARG, "contrast must lie in [0, 1]");
+  if (mode != BSGP_DEBLEND_LINEAR && mode != BSGP_DEBLEND_EXPONENTIAL)
+    return fail(BSGP_ERR_ARG, "mode must be BSGP_DEBLEND_LINEAR or BSGP_DEBLEND_EXPONENTIAL");
+  if (connectivity != 4 && connectivity != 8)
+    return fail(BSGP_ERR_ARG, "connectivity must be 4 or 8");
+  if (int rc = seg_shape(B, H, W)) return rc;
+  DeblendArgs a{};
+  a.data = data, a.labels = labels, a.nlabels = nlabels, a.icols = int_cols, a.sel = select;
+  a.B = B, a.H = H, a.W = W, a.cap = cap, a.npixels = npixels, a.nlevels = nlevels;
+  a.conn = connectivity, a.mode = mode, a.contrast = contrast;
+  a.labels_out = labels_out, a.nlabels_out = nlabels_out, a.status = status_out;
+  a.large = lds_max_box >= 0;
+  a.lds_max_box = a.large ? lds_max_box : kDeblendMaxBox;
+  hipStream_t s = (hipStream_t)stream;
+  // stream-ordered workspace: the call stays asynchronous.  The global-memory
+  // path adds 32 bytes per pixel (one double and six ints), sized by B, H, W
+  // alone and never initialised.
+  const size_t rows = (size_t)B * cap, px = a.large ? (size_t)B * H * W : 0;
+  void* w = nullptr;
+  HIP_TRY(hipMallocAsync(&w, px * (sizeof(double) + 6 * sizeof(int)) + 2 * rows * sizeof(int), s));
+  a.hkey = static_cast<double*>(w);
+  a.lev = reinterpret_cast<int*>(a.hkey + px);
+  a.reg = a.lev + px, a.cnt = a.reg + px, a.kept = a.cnt + px, a.mk = a.kept + px;
+  a.hidx = a.mk + px;
+  a.nchild = a.hidx + px;
+  a.base = a.nchild + rows;
+  hipError_t e = hipMemsetAsync(a.nchild, 0, rows * sizeof(int), s);
+  if (e == hipSuccess) e = hipMemsetAsync(status_out, 0, (size_t)B * sizeof(int), s);
+  if (e == hipSuccess) e = launch_deblend(a, s);
+  const hipError_t ef = hipFreeAsync(w, s);
+  if (e != hipSuccess) return fail(BSGP_ERR_HIP, std::string("deblend launch: ") + hipGetErrorString(e));
+  HIP_TRY(ef);
+  return BSGP_OK;
+}
+
+int bsgp_deblend_sources(const double* data, const int32_t* labels, int32_t B, int32_t H, int32_t W,
+                         int32_t cap, const int32_t* nlabels, const int32_t* int_cols,
+                         const uint8_t* select, int32_t npixels, int32_t nlevels, double contrast,
+                         int32_t mode, int32_t connectivity, int32_t* labels_out,
+                         int32_t* nlabels_out, int32_t* status_out, void* stream) {
+  return deblend_sources(data, labels, B, H, W, cap, nlabels, int_cols, select, npixels, nlevels,
+                         contrast, mode, connectivity, -1, labels_out, nlabels_out, status_out,
+                         stream);
+}
+
+int bsgp_deblend_sources_large(const double* data, const int32_t* labels, int32_t B, int32_t H,
+                               int32_t W, int32_t cap, const int32_t* nlabels,
+                               const int32_t* int_cols, const uint8_t* select, int32_t npixels,
+                               int32_t nlevels, double contrast, int32_t mode,
+                               int32_t connectivity, int32_t lds_max_box, int32_t* labels_out,
+                               int32_t* nlabels_out, int32_t* status_out, void* stream) {
+  if (lds_max_box < 0 || lds_max_box > BSGP_DEBLEND_MAX_BOX)
+    return fail(BSGP_ERR_ARG, "lds_max_box must lie in 0 .. BSGP_DEBLEND_MAX_BOX");
+  return deblend_sources(data, labels, B, H, W, cap, nlabels, int_cols, select, npixels, nlevels,
+                         contrast, mode, connectivity, lds_max_box, labels_out, nlabels_out,
+                         status_out, stream);
+}
+
+int bsgp_radial_profile(const void* data, int32_t dtype, int32_t B, int32_t H, int32_t W,
+                        const double* centers, int32_t rcap, double* prof, int32_t* len,
+                        void* stream) {
+  if (!data) return fail(BSGP_ERR_ARG, "data is NULL");
+  if (!centers) return fail(BSGP_ERR_ARG, "centers is NULL");
+  if (!prof || !len) return fail(BSGP_ERR_ARG, "prof / len is NULL");
+  if (dtype != BSGP_DTYPE_F32 && dtype != BSGP_DTYPE_F64)
+    return fail(BSGP_ERR_ARG, "dtype must be BSGP_DTYPE_F32 or BSGP_DTYPE_F64");
+  if (B < 1 || H < 1 || W < 1) return fail(BSGP_ERR_ARG, "B, H and W must be >= 1");
+  if (rcap < 1) return fail(BSGP_ERR_ARG, "rcap must be >= 1");
+  char msg[160];
+  if ((int64_t)H * W > kStampMaxPixels) {
+    snprintf(msg, sizeof msg, "stamp of %lld pixels: a stamp holds at most %d (H * W <= %d)",
+             (long long)H * W, kStampMaxPixels, kStampMaxPixels);
+    return fail(BSGP_ERR_UNSUPPORTED, msg);
+  }
+  if (rcap > kStampMaxBins) {
+    snprintf(msg, sizeof msg, "%d radial bins: a profile holds at most %d", rcap, kStampMaxBins);
+    return fail(BSGP_ERR_UNSUPPORTED, msg);
+  }
+  StampProfArgs a{};
+  a.data = data, a.centers = centers, a.B = B, a.H = H, a.W = W, a.rcap = rcap;
+  a.prof = prof, a.len = len;
+  HIP_TRY(launch_stamp_radprof(a, dtype == BSGP_DTYPE_F32, (hipStream_t)stream));
+  return BSGP_OK;
+}
+
+int bsgp_fit_gauss1d(const double* prof, const int32_t* len, int32_t B, int32_t rcap,
+                     const double* fwhm, double* fitted, double* params, double* perr,
+                     int32_t* info, void* stream) {
+  if (!prof || !len || !fwhm) return fail(BSGP_ERR_ARG, "prof / len / fwhm is NULL");
+  if (!fitted || !params || !perr || !info)
+    return fail(BSGP_ERR_ARG, "fitted / params / perr / info is NULL");
+  if (B < 1 || rcap < 1) return fail(BSGP_ERR_ARG, "B and rcap must be >= 1");
+  if (rcap > kStampMaxBins) {
+    char msg[128];
+    snprintf(msg, sizeof msg, "profiles of %d values: a profile holds at most %d", rcap,
+             kStampMaxBins);
+    return fail(BSGP_ERR_UNSUPPORTED, msg);
+  }
+  StampFitArgs a{};
+  a.prof = prof, a.len = len, a.fwhm = fwhm, a.B = B, a.rcap = rcap;
+  a.fitted = fitted, a.params = params, a.perr = perr, a.info = info;
+  HIP_TRY(launch_stamp_fit(a, (hipStream_t)stream));
+  return BSGP_OK;
+}
+
+int bsgp_wasserstein1(const double* u, const int32_t* ulen, const double* v, const int32_t* vlen,
+                      int32_t B, int32_t rcap, double* out, void* stream) {
+  if (!u || !v) return fail(BSGP_ERR_ARG, "u / v is NULL");
+  if (!out) return fail(BSGP_ERR_ARG, "out is NULL");
+  if (B < 1 || rcap < 1) return fail(BSGP_ERR_ARG, "B and rcap must be >= 1");
+  if (rcap > kStampMaxBins) {
+    char msg[128];
+    snprintf(msg, sizeof msg, "samples of %d values: a sample holds at most %d", rcap,
+             kStampMaxBins);
+    return fail(BSGP_ERR_UNSUPPORTED, msg);
+  }
+  StampW1Args a{};
+  a.u = u, a.v = v, a.ulen = ulen, a.vlen = vlen, a.B = B, a.rcap = rcap, a.out = out;
+  a.P = 2;
+  while (a.P < 2 * rcap) a.P *= 2;
+  HIP_TRY(launch_stamp_w1(a, (hipStream_t)stream));
+  return BSGP_OK;
+}
+
+int bsgp_beta_div(int64_t n, const double* y, const double* x, double beta, double* out,
+                  void* stream) {
+  if (n < 1 || n > 0x7fffffff || !y || !x || !out) return fail(BSGP_ERR_ARG, "bad arguments");
+  HIP_TRY(launch_beta_div((int)n, y, x, beta, out, (hipStream_t)stream));
+  return BSGP_OK;
+}
+
+int bsgp_beta_div_deriv(int64_t n, const double* y, const double* x, double beta, double* out,
+                        void* stream) {
+  if (n < 1 || !y || !x || !out) return fail(BSGP_ERR_ARG, "bad arguments");
+  HIP_TRY(launch_beta_div_deriv(n, y, x, beta, out, (hipStream_t)stream));
+  return BSGP_OK;
+}
+
+int bsgp_beta_div_grad_parts(int64_t n, const double* den, const double* gn, double beta,
+                             double* pow1, double* w, void* stream) {
+  if (n < 1 || !den || !gn || !pow1 || !w) return fail(BSGP_ERR_ARG, "bad arguments");
+  HIP_TRY(launch_grad_parts(n, den, gn, beta, pow1, w, (hipStream_t)stream));
+  return BSGP_OK;
+}
+
+}  // extern "C"

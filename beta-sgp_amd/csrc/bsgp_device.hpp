@@ -104,7 +104,7 @@ __device__ __forceinline__ const cd* tf_of(const GT& G, int img, int transpose) 
 // Compile-time geometry (the geometry policy of the per-wave row and column
 // helpers, which take the geometry as a template type: the runtime Geo, or
 // this).  The same member names as Geo, as constants derived by the formulas
-// of bsgp_plan_create for a per-wave plan whose transforms and twiddle tables
+// of plan_layout (bsgp_layout.hpp) for a per-wave plan whose transforms and twiddle tables
 // fit the LDS at four workgroups' budget; only the TF pointers stay runtime
 // values.  The host selects it for a solve only when the plan's own values
 // equal these (static_geo_plan, bsgp_kernels.hpp), so a phase instantiated on

@@ -1,5 +1,5 @@
 // bsgp_internal.hpp — structures shared by the kernels (bsgp_solver.hip) and
-// the C-ABI host layer (bsgp_api.hip).  Not part of the public interface.
+// the C-ABI host layer (bsgp_plan.hip, bsgp_solve.hip, bsgp_apps.hip).  Not part of the public interface.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -50,7 +50,7 @@ struct ImgState {
 // scratch: the projection state stays live), at the start of k_ls 1 % (spills
 // at 168 VGPRs).  Teams launch k_col for both.
 
-// numpy float32 reduction program of a plan's N (bsgp_api.hip pairwise_program):
+// numpy float32 reduction program of a plan's N (bsgp_layout.hpp pairwise_program):
 // [nleaf][2] leaves (start, len), [nnode][2] node operands (value indices),
 // [nlev + 1] level offsets into the nodes, [nchunk] root value of each chunk.
 struct PwProg {

@@ -392,7 +392,7 @@ __device__ __forceinline__ size_t lds_fft_bytes_of(const SolveArgs& A) {
   double* red = reinterpret_cast<double*>(smem + (A).g.tw2 + (A).lds_fft_bytes)
 
 // numpy's float32 np.sum of term(i) for i < N, in numpy's exact order (the
-// plan's PwProg, bsgp_api.hip pairwise_program): the leaves by the team's
+// plan's PwProg, bsgp_layout.hpp pairwise_program): the leaves by the team's
 // threads (each a numpy leaf: 8 strided float32 accumulators), the inner nodes
 // level by level with a team barrier between levels, then the chunk fold
 // res = res + root from 0.  `vals` is float scratch in HBM (leaves + nodes).
@@ -1182,7 +1182,7 @@ __device__ __forceinline__ void ls_phase(const SolveArgs& A, int img) {
   };
   double fr = st.Fold[0];
   for (int k = 1; k < P.M; ++k) fr = py_max2(fr, st.Fold[k]);
-  const int ls_cap = A.ls_cap;  // trial cap (bsgp_api.hip): never reached for 0 < beta < 1
+  const int ls_cap = A.ls_cap;  // trial cap (bsgp_solve.hip): never reached for 0 < beta < 1
   Objective obj = make_obj(A, st.beta);
   double lam = 1.0;
   double f_acc = 0.0;
@@ -2352,7 +2352,7 @@ inline const void* ls_kernel(int K, int mode, bool adapt) {
 }
 
 // Team kernels (T > 1 workgroups per image spin on each other) need every
-// workgroup of the grid resident at once.  choose_team (bsgp_api.hip) sizes
+// workgroup of the grid resident at once.  choose_team (bsgp_solve.hip) sizes
 // teams from the occupancy the runtime reports for every team kernel of the
 // plan's build (team_resident_per_cu), so the grid fits the idle device; the
 // barrier's bounded spin turns a violation (another tenant holding CUs) into

@@ -13,7 +13,7 @@
 //
 // Every kBlock-dependent type and kernel lives in its own namespace
 // (bsgp_c512) so the two builds do not collide; the host reaches them through
-// the C-linkage launchers below, which take the SolveArgs of bsgp_api.hip
+// the C-linkage launchers below, which take the SolveArgs of bsgp_solve.hip
 // (same header, same layout: checked at plan creation by bsgp_c512_args_size).
 #include <hip/hip_runtime.h>
 

@@ -171,3 +171,23 @@ def test_device_scope_restores_current_device(sgpmod):
     t.join()
     assert torch.cuda.current_device() == dev
     assert float(torch.ones(3, device="cuda").sum()) == 3.0
+
+
+@pytest.mark.parametrize("H,kh,conv", [(16, 5, "linear"), (16, 16, "circular")])
+def test_plan_info_is_plan_layout(sgpmod, H, kh, conv):
+    """bsgp_plan_info of a created plan equals the fields of bsgp_plan_layout
+    (the host-only diagnostic, tests/test_plan_layout.py) for the same
+    arguments: the diagnostic reports what plan creation really uses."""
+    import ctypes
+
+    import _bsgp
+    mode = _bsgp.BSGP_CONV_CIRCULAR if conv == "circular" else _bsgp.BSGP_CONV_LINEAR_FILL
+    psf = np.full((kh, kh), 1.0 / (kh * kh))
+    L = _bsgp.lib()
+    L.bsgp_plan_layout.argtypes = [ctypes.c_int32] * 6 + [ctypes.c_void_p, ctypes.c_int32]
+    lay = np.zeros(22, np.int64)
+    _bsgp.check(L.bsgp_plan_layout(H, H, kh, kh, mode, _bsgp.BSGP_STORAGE_F64, lay.ctypes.data, 22))
+    plan = _bsgp.Plan(H, H, psf, mode)
+    # out[2] P, out[3] Q, out[7] nfw, out[21] slot_stride in doubles
+    assert (plan.P, plan.Q, plan.fft_waves) == (lay[2], lay[3], lay[7])
+    assert plan.slot_bytes == 8 * lay[21]

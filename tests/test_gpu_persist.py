@@ -133,7 +133,7 @@ def test_persistent_cooperative_plans_bitwise(sgpmod, case):
     if case != "app_f32":
         gns = gns.astype(np.float64)
     # 675-point grid: per-wave buffers 4 waves x 2 x 677 x 16 B + 1.25 KB = 87.9 KB exceed
-    # the 81.7 KB of two workgroups per CU, so the plan is cooperative (bsgp_api.hip)
+    # the 81.7 KB of two workgroups per CU, so the plan is cooperative (bsgp_layout.hpp)
     plan = _bsgp.get_plan(640, 640, psf, _bsgp.BSGP_CONV_LINEAR_FILL)
     assert plan.P == plan.Q == 675
     kw.update(MAXIT=8, team=1)

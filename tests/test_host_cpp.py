@@ -11,7 +11,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "beta-sgp_amd", "csrc")
 
 
-@pytest.mark.parametrize("src", ["fft_core_test.cpp", "math_test.cpp", "libmf_test.cpp"])
+@pytest.mark.parametrize("src", ["fft_core_test.cpp", "math_test.cpp", "libmf_test.cpp",
+                                 "plan_layout_test.cpp"])
 def test_host_cpp(src, tmp_path):
     exe = tmp_path / src.replace(".cpp", "")
     # -ffp-contract=off: the same rounding as the gfx950 build

@@ -208,7 +208,7 @@ def test_oracle_application_path(name):
 
 
 def _pairwise_model(a, prog, counts):
-    """Evaluates the plans' numpy float32 reduction program (bsgp_api.hip
+    """Evaluates the plans' numpy float32 reduction program (bsgp_layout.hpp
     pairwise_program) in float32, the way the setup kernel does."""
     nleaf, nnode, nlev, nchunk = counts
     lv = prog[:2 * nleaf].reshape(-1, 2)

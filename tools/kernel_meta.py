@@ -11,8 +11,9 @@ allow-list these must stay within.
 
     python3 tools/kernel_meta.py --diff OLD NEW
 
-compares two builds (objects or libraries) code object by code object: the
-digests of .text and .rodata, and per kernel symbol whether its bytes in .text
+compares two builds (objects or libraries) code object by code object (paired
+by the kernels they hold, not by position: the link order follows the file
+names of csrc/): the digests of .text and .rodata, and per kernel symbol whether its bytes in .text
 and its metadata are equal (likewise the bytes of the device functions the
 kernels call), plus the kernels on one side only.  Exit status 0 when every
 kernel and function present on both sides is identical.  Bytes and sizes only:
@@ -130,7 +131,18 @@ def diff(old, new, arch="gfx950"):
     a, b = code_objects(old, arch), code_objects(new, arch)
     same = len(a) == len(b)
     print(f"code objects: {len(a)} / {len(b)}")
-    for i, (x, y) in enumerate(zip(a, b)):
+    # each old code object with the new one that shares the most kernels with it
+    rest, pairs = list(b), []
+    for x in a:
+        kx = set(_kernels_of(x))
+        y = max(rest, key=lambda c: len(kx & set(_kernels_of(c))), default=None)
+        if y is None or not kx & set(_kernels_of(y)):
+            same = False
+            print(f"no counterpart of the code object holding {sorted(kx)[:1]}")
+            continue
+        rest.remove(y)
+        pairs.append((x, y))
+    for i, (x, y) in enumerate(pairs):
         for sec in (".text", ".rodata"):
             dx, dy = (hashlib.sha256(_section(c, sec) or b"").hexdigest()[:16] for c in (x, y))
             print(f"[{i}] {sec:8s} {dx} {dy} {'equal' if dx == dy else 'DIFFERENT'}")
