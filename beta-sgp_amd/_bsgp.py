@@ -40,6 +40,10 @@ BSGP_DEBLEND_LINEAR, BSGP_DEBLEND_EXPONENTIAL = 0, 1
 BSGP_DEBLEND_OVER_CAP, BSGP_DEBLEND_BAD_LABEL = 1, 2
 BSGP_LOCALBKG_MAX = 8192  # values of one local-background annulus in LDS (include/bsgp.h)
 BSGP_LOCALBKG_FEW, BSGP_LOCALBKG_OVER_CAP = 1, 2
+BSGP_MATCH_LDS_MAX = 4096  # cap1 + cap2 of the cross-match's LDS path (include/bsgp.h)
+BSGP_MATCH_MAX = 16384  # rows of one catalogue in a cross-match
+BSGP_MATCH_AUTO, BSGP_MATCH_LDS, BSGP_MATCH_GLOBAL = 0, 1, 2
+BSGP_MATCH_NONFINITE, BSGP_MATCH_OVER_CAP = 1, 2
 
 
 class BsgpError(RuntimeError):
@@ -180,6 +184,8 @@ def lib():
             L.bsgp_segment_local_background.argtypes = [vp, i32, vp, i32, i32, i32, i32, vp, vp,
                                                         vp, dbl, dbl, i32, i32, i32, vp, vp, vp,
                                                         vp]
+            L.bsgp_match_catalogs.argtypes = [vp, vp, i32, vp, i32, i32, vp, vp, vp, i32, vp, i32,
+                                              i32, vp, i32, dbl, i32, vp, vp, vp, vp, vp, vp]
             L.bsgp_radial_profile.argtypes = [vp, i32, i32, i32, i32, vp, i32, vp, vp, vp]
             L.bsgp_fit_gauss1d.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]
             L.bsgp_wasserstein1.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp]
@@ -195,7 +201,8 @@ def lib():
                          "bsgp_segment_catalog", "bsgp_plan_set_static_geo",
                          "bsgp_plan_static_geo", "bsgp_radial_profile", "bsgp_fit_gauss1d",
                          "bsgp_wasserstein1", "bsgp_deblend_sources",
-                         "bsgp_deblend_sources_large", "bsgp_segment_local_background"]:
+                         "bsgp_deblend_sources_large", "bsgp_segment_local_background",
+                         "bsgp_match_catalogs"]:
                 getattr(L, name).restype = ctypes.c_int
             if L.bsgp_abi_version() != ABI_VERSION:
                 raise BsgpError(-3, f"{LIB_PATH} has ABI {L.bsgp_abi_version()}, this binding "
@@ -213,7 +220,7 @@ EXPORTED = ["bsgp_plan_create", "bsgp_plan_create_checked", "bsgp_plan_destroy",
             "bsgp_convolve2d", "bsgp_detect_sources", "bsgp_segment_catalog",
             "bsgp_plan_set_static_geo", "bsgp_plan_static_geo", "bsgp_radial_profile",
             "bsgp_fit_gauss1d", "bsgp_wasserstein1", "bsgp_deblend_sources",
-            "bsgp_deblend_sources_large", "bsgp_segment_local_background"]
+            "bsgp_deblend_sources_large", "bsgp_segment_local_background", "bsgp_match_catalogs"]
 
 
 def check(rc):

@@ -1,10 +1,12 @@
 // bsgp_apps.hip — the entry points of the C-ABI host layer that take no plan
 // (declared in include/bsgp.h): the projection, tiles, FITS pixels, PSF stamps,
 // sky background, convolution, detection, catalogue, local background,
-// deblending, star-stamp metrics and the divergences.  Each validates its
-// arguments and launches its kernels.
+// deblending, catalogue cross-match, star-stamp metrics and the divergences.
+// Each validates its arguments and launches its kernels.
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
+#include <limits>
 #include <string>
 
 #include "bsgp_host.hpp"
@@ -339,6 +341,91 @@ int bsgp_deblend_sources_large(const double* data, const int32_t* labels, int32_
   return deblend_sources(data, labels, B, H, W, cap, nlabels, int_cols, select, npixels, nlevels,
                          contrast, mode, connectivity, lds_max_box, labels_out, nlabels_out,
                          status_out, stream);
+}
+
+namespace {
+// M2 on the host: the float64 after the largest one whose square root is <=
+// max_sep.  sqrt is monotone and max_sep^2 is rounded once, so the walk from
+// it takes a step or two.
+double match_d2_limit(double max_sep) {
+  double t = max_sep * max_sep;
+  if (std::isinf(t)) t = std::numeric_limits<double>::max();
+  while (t > 0.0 && std::sqrt(t) > max_sep) t = std::nextafter(t, 0.0);
+  for (double u = std::nextafter(t, HUGE_VAL); std::isfinite(u) && std::sqrt(u) <= max_sep;
+       u = std::nextafter(t, HUGE_VAL))
+    t = u;
+  return std::nextafter(t, HUGE_VAL);
+}
+
+// threads per workgroup of the match kernels: BSGP_MATCH_BLOCK (a multiple of 64
+// in 64..1024; tools/match_timing.py's knob), else the fastest of 64 .. 1024 on
+// every workload of profiles/match: 1024 in LDS, 512 in global memory
+int match_block(bool lds, int rows) {
+  int block = lds ? 1024 : 512;
+  if (const char* e = getenv("BSGP_MATCH_BLOCK")) {
+    const int v = atoi(e);
+    if (v >= 64 && v <= 1024 && v % 64 == 0) block = v;
+  }
+  const int need = (rows + 63) / 64 * 64;  // no wave without a row
+  return need < block ? need : block;
+}
+}  // namespace
+
+int bsgp_match_catalogs(const double* x1, const double* y1, int32_t stride1, const int32_t* valid1,
+                        int32_t vstride1, int32_t cap1, const int32_t* n1, const double* x2,
+                        const double* y2, int32_t stride2, const int32_t* valid2, int32_t vstride2,
+                        int32_t cap2, const int32_t* n2, int32_t B, double max_sep, int32_t path,
+                        int32_t* match1_out, int32_t* match2_out, double* sep1_out,
+                        int32_t* npairs_out, int32_t* status_out, void* stream) {
+  if (!(max_sep >= 0.0) || !std::isfinite(max_sep))
+    return fail(BSGP_ERR_ARG, "max_sep must be finite and >= 0");
+  if (cap1 < 1 || cap2 < 1) return fail(BSGP_ERR_ARG, "cap1 and cap2 must be >= 1");
+  if (B < 0) return fail(BSGP_ERR_ARG, "B must be >= 0");
+  if (stride1 < 1 || stride2 < 1) return fail(BSGP_ERR_ARG, "stride1 and stride2 must be >= 1");
+  if (path != BSGP_MATCH_AUTO && path != BSGP_MATCH_LDS && path != BSGP_MATCH_GLOBAL)
+    return fail(BSGP_ERR_ARG, "path must be BSGP_MATCH_AUTO, BSGP_MATCH_LDS or BSGP_MATCH_GLOBAL");
+  if (B == 0) return BSGP_OK;  // no image: nothing to do, no pointer is followed
+  if (!x1 || !y1 || !x2 || !y2) return fail(BSGP_ERR_ARG, "x1 / y1 / x2 / y2 is NULL");
+  if ((valid1 && vstride1 < 1) || (valid2 && vstride2 < 1))
+    return fail(BSGP_ERR_ARG, "vstride1 and vstride2 must be >= 1 where valid is given");
+  if (!match1_out || !match2_out || !sep1_out || !npairs_out || !status_out)
+    return fail(BSGP_ERR_ARG,
+                "match1_out / match2_out / sep1_out / npairs_out / status_out is NULL");
+  char msg[160];
+  if (cap1 > kMatchMax || cap2 > kMatchMax) {
+    snprintf(msg, sizeof msg, "catalogues of %d and %d rows: a catalogue holds at most %d", cap1,
+             cap2, kMatchMax);
+    return fail(BSGP_ERR_UNSUPPORTED, msg);
+  }
+  const bool fits = (int64_t)cap1 + cap2 <= kMatchLdsMax;
+  if (path == BSGP_MATCH_LDS && !fits) {
+    snprintf(msg, sizeof msg, "cap1 + cap2 = %d: the LDS path holds at most %d rows", cap1 + cap2,
+             kMatchLdsMax);
+    return fail(BSGP_ERR_UNSUPPORTED, msg);
+  }
+  const bool lds = path == BSGP_MATCH_LDS || (path == BSGP_MATCH_AUTO && fits);
+  MatchArgs a{};
+  a.c1 = MatchCat{x1, y1, valid1, n1, stride1, valid1 ? vstride1 : 1, cap1};
+  a.c2 = MatchCat{x2, y2, valid2, n2, stride2, valid2 ? vstride2 : 1, cap2};
+  a.d2_lim = match_d2_limit(max_sep);
+  a.match1 = match1_out, a.match2 = match2_out, a.sep1 = sep1_out;
+  a.npairs = npairs_out, a.status = status_out;
+  hipStream_t s = (hipStream_t)stream;
+  const int rows = match_rows(cap1, cap2), block = match_block(lds, rows);
+  if (lds) {
+    HIP_TRY(launch_match(a, B, true, block, s));
+    return BSGP_OK;
+  }
+  // stream-ordered workspace: the call stays asynchronous
+  void* w = nullptr;
+  HIP_TRY(hipMallocAsync(&w, (size_t)B * rows * kMatchRowBytes, s));
+  a.ws_xy = static_cast<double*>(w);
+  a.ws_state = reinterpret_cast<int*>(a.ws_xy + (size_t)B * rows * 2);
+  const hipError_t e = launch_match(a, B, false, block, s);
+  const hipError_t ef = hipFreeAsync(w, s);
+  if (e != hipSuccess) return fail(BSGP_ERR_HIP, std::string("match launch: ") + hipGetErrorString(e));
+  HIP_TRY(ef);
+  return BSGP_OK;
 }
 
 int bsgp_radial_profile(const void* data, int32_t dtype, int32_t B, int32_t H, int32_t W,

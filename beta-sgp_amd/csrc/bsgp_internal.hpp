@@ -222,6 +222,32 @@ struct LocalBkgArgs {
   int* status;  // [B]: BSGP_LOCALBKG_* bits (zeroed first)
 };
 hipError_t launch_localbkg(const LocalBkgArgs& a, int f32, hipStream_t s);
+// ---- catalogue cross-match (bsgp_match.hip) ----------
+constexpr int kMatchLdsMax = BSGP_MATCH_LDS_MAX;  // cap1 + cap2 of the LDS path
+constexpr int kMatchMax = BSGP_MATCH_MAX;         // rows of one catalogue
+// One side's columns: element (b, r) is ptr[(b * cap + r) * stride].
+struct MatchCat {
+  const double *x, *y;
+  const int* valid;  // > 0 = the row takes part, or nullptr: every row
+  const int* n;      // [B], or nullptr: cap
+  int stride, vstride, cap;
+};
+struct MatchArgs {
+  MatchCat c1, c2;
+  double d2_lim;  // a candidate has d2 < d2_lim: the float64 after the largest whose sqrt <= max_sep
+  int *match1, *match2;  // [B][cap1], [B][cap2]
+  double* sep1;          // [B][cap1]
+  int *npairs, *status;  // [B]
+  // the global path's workspace, per image: (x, y) of match_rows(cap1, cap2)
+  // rows, then their best and match entries
+  double* ws_xy;
+  int* ws_state;
+};
+// rows of the kernels' joint index space: catalogue 2 starts on a wave boundary
+__host__ __device__ inline int match_rows(int n1, int n2) { return ((n1 + 63) & ~63) + n2; }
+constexpr size_t kMatchRowBytes = 2 * sizeof(double) + 2 * sizeof(int);
+// block: threads per workgroup, a multiple of 64 up to 1024
+hipError_t launch_match(const MatchArgs& a, int B, bool lds, int block, hipStream_t s);
 // ---- deblending (bsgp_deblend.hip) -----------------------------
 constexpr int kDeblendMaxBox = BSGP_DEBLEND_MAX_BOX;  // box pixels of one parent (LDS)
 struct DeblendArgs {

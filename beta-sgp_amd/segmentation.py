@@ -35,6 +35,7 @@ over segments depends on the deblending: the reference's flux constraint is
 ``localbkg_width=5`` together with ``deblend=True``.  The default is 0
 everywhere, which leaves the columns as they were.
 """
+import ctypes
 import warnings
 
 import numpy as np
@@ -773,3 +774,258 @@ def catalog_flux_fraction_score(gn, box_size=60, n_pixels_orig=5, n_pixels_resto
 
     score.batch = batch
     return score
+
+
+# ---- cross-match of two catalogues (bsgp_match_catalogs) ----
+MATCH_LDS_MAX, MATCH_MAX = _B.BSGP_MATCH_LDS_MAX, _B.BSGP_MATCH_MAX
+MATCH_PATHS = {None: _B.BSGP_MATCH_AUTO, "auto": _B.BSGP_MATCH_AUTO, "lds": _B.BSGP_MATCH_LDS,
+               "global": _B.BSGP_MATCH_GLOBAL}
+METRIC_COLUMNS = ("segment_flux", "fwhm", "ellipticity")
+
+
+def check_match_args(max_sep, path=None, batch1=1, batch2=1, cap1=1, cap2=1):
+    """The argument checks of match_catalogs (host only): ``max_sep`` a finite
+    number >= 0, ``path`` None / 'auto', 'lds' or 'global', both sides of one
+    batch size, at most ``MATCH_MAX`` rows per catalogue and, on the LDS path,
+    ``MATCH_LDS_MAX`` rows in both.  Returns (max_sep, the path's code)."""
+    s = max_sep
+    if isinstance(s, (bool, np.bool_)) or not isinstance(s, (int, float, np.integer, np.floating)) \
+            or not np.isfinite(s) or s < 0:
+        raise ValueError(f"max_sep must be a finite number >= 0, got {max_sep!r}")
+    if not isinstance(path, (str, type(None))) or path not in MATCH_PATHS:
+        raise ValueError(f"path must be None, 'auto', 'lds' or 'global', got {path!r}")
+    if batch1 != batch2:
+        raise ValueError(f"the catalogues are batches of {batch1} and {batch2} images: both sides "
+                         "must have the same batch size")
+    if max(cap1, cap2) > MATCH_MAX:
+        raise ValueError(f"catalogues of {cap1} and {cap2} rows: a catalogue holds at most "
+                         f"{MATCH_MAX}")
+    if path == "lds" and cap1 + cap2 > MATCH_LDS_MAX:
+        raise ValueError(f"catalogues of {cap1} + {cap2} rows: path='lds' holds at most "
+                         f"{MATCH_LDS_MAX} in both")
+    return float(s), MATCH_PATHS[path]
+
+
+def _match_items(cat):
+    """(the images of a catalogue as a list of unbatched catalogues, whether it
+    is a batch).  A list is a batch, a SourceCatalog what it was made as."""
+    if isinstance(cat, SourceCatalog) and cat.batched:
+        return [{k: cat[k][b] for k in ("xcentroid", "ycentroid", "area", "label")}
+                for b in range(len(cat.nlabels))], True
+    if isinstance(cat, list):
+        if any(isinstance(c, list) or getattr(c, "batched", False) for c in cat):
+            raise ValueError("a batch is a list of unbatched catalogues")
+        return cat, True
+    return [cat], False
+
+
+def _column(cat, name):
+    try:
+        v = cat[name]
+    except (KeyError, TypeError, IndexError, ValueError):
+        return None
+    return np.asarray(getattr(v, "value", v))
+
+
+def _xy_of(cat):
+    """(x, y, area or None, label or None) of one unbatched catalogue: an
+    (x, y) tuple, or anything indexable by 'xcentroid' / 'ycentroid' (and,
+    where it has them, 'area' and 'label')."""
+    if isinstance(cat, tuple):
+        if len(cat) != 2:
+            raise ValueError(f"a coordinate tuple is (x, y), got {len(cat)} entries")
+        x, y, area, label = np.asarray(cat[0]), np.asarray(cat[1]), None, None
+    else:
+        x, y = _column(cat, "xcentroid"), _column(cat, "ycentroid")
+        if x is None or y is None:
+            raise ValueError("a catalogue is a SourceCatalog, an (x, y) tuple or indexable by "
+                             f"'xcentroid' / 'ycentroid', got {type(cat).__name__}")
+        area, label = _column(cat, "area"), _column(cat, "label")
+    x, y = x.astype(np.float64).reshape(-1), y.astype(np.float64).reshape(-1)
+    if x.shape != y.shape or (area is not None and area.shape != x.shape):
+        raise ValueError(f"the columns of a catalogue differ in length ({len(x)} x, {len(y)} y)")
+    return x, y, area, label
+
+
+class _MatchSide:
+    """One side of a match on the device: column pointers as
+    bsgp_match_catalogs takes them, the host row counts and the labels."""
+
+    def __init__(self, cat):
+        torch = _B.torch
+        if isinstance(cat, SourceCatalog) and hasattr(cat, "f64_cols"):
+            # device columns (bsgp_segment_catalog's layout), matched in place
+            fc, ic = cat.f64_cols, cat.int_cols
+            self.batched = cat.batched
+            self.n = np.atleast_1d(np.asarray(cat.nlabels, dtype=np.int32))
+            self.B, self.cap = int(fc.shape[0]), int(fc.shape[1])
+            self.x = ctypes.c_void_p(fc.data_ptr() + 3 * 8)
+            self.y = ctypes.c_void_p(fc.data_ptr() + 4 * 8)
+            self.valid, self.stride, self.vstride = _B._ptr(ic), 8, 5
+            self.labels = [np.arange(1, k + 1, dtype=np.int32) for k in self.n]
+            self._keep = (fc, ic)
+        else:
+            items, self.batched = _match_items(cat)
+            cols = [_xy_of(c) for c in items]
+            self.B = len(cols)
+            self.n = np.array([len(c[0]) for c in cols], dtype=np.int32)
+            self.cap = max(1, int(self.n.max())) if self.B else 1
+            xy = np.zeros((2, self.B, self.cap))
+            va = None if all(c[2] is None for c in cols) else np.ones((self.B, self.cap), np.int32)
+            for b, c in enumerate(cols):
+                xy[0, b, :len(c[0])], xy[1, b, :len(c[0])] = c[0], c[1]
+                if c[2] is not None:
+                    va[b, :len(c[0])] = np.asarray(c[2]) > 0
+            xyd = torch.from_numpy(xy).to("cuda")
+            vad = None if va is None else torch.from_numpy(va).to("cuda")
+            self.x, self.y = _B._ptr(xyd[0]), _B._ptr(xyd[1])
+            self.valid, self.stride, self.vstride = _B._ptr(vad), 1, 1
+            self.labels = [c[3] for c in cols]
+            self._keep = (xyd, vad)
+        self.nd = torch.from_numpy(np.ascontiguousarray(self.n)).to("cuda")
+
+    def args(self):
+        return (self.x, self.y, self.stride, self.valid, self.vstride, self.cap, _B._ptr(self.nd))
+
+
+class CatalogMatch:
+    """Result of :func:`match_catalogs`.  ``idx1`` / ``idx2``: the 0-based rows
+    of the pairs in catalogue 1 / 2, ordered by ``idx1`` (the order of the
+    reference's published tables); ``separation`` of each pair; ``n_pairs``;
+    ``unmatched1`` / ``unmatched2``: the rows without a partner (rows that took
+    no part included); ``match1`` / ``match2``: per row the partner's row or
+    -1; ``sep1``: per row of catalogue 1 the separation or NaN; ``labels1`` /
+    ``labels2``: the pairs' labels where the catalogue has ``label`` (else
+    ``None``); ``status``: the ``BSGP_MATCH_*`` bits.  For a batch every
+    attribute is a list over the images (``n_pairs`` and ``status`` int
+    arrays).  With ``device_out=True`` ``match1_dev`` / ``match2_dev`` /
+    ``sep1_dev`` [B, cap] and ``n_pairs_dev`` / ``status_dev`` [B] are the CUDA
+    tensors the kernel wrote."""
+
+    def __init__(self, match1, match2, sep1, status, labels1=None, labels2=None, batched=False):
+        B = len(match1)
+        labels1, labels2 = labels1 or [None] * B, labels2 or [None] * B
+        cols = {k: [] for k in ("idx1", "idx2", "separation", "unmatched1", "unmatched2",
+                                "labels1", "labels2")}
+        for m1, m2, sp, l1, l2 in zip(match1, match2, sep1, labels1, labels2):
+            i = np.flatnonzero(m1 >= 0)
+            cols["idx1"].append(i), cols["idx2"].append(m1[i].astype(np.int64))
+            cols["separation"].append(sp[i])
+            cols["unmatched1"].append(np.flatnonzero(m1 < 0))
+            cols["unmatched2"].append(np.flatnonzero(m2 < 0))
+            cols["labels1"].append(None if l1 is None else np.asarray(l1)[i])
+            cols["labels2"].append(None if l2 is None else np.asarray(l2)[m1[i]])
+        cols.update(match1=list(match1), match2=list(match2), sep1=list(sep1))
+        self.batched = batched
+        for k, v in cols.items():
+            setattr(self, k, v if batched else v[0])
+        n = np.array([len(i) for i in cols["idx1"]], dtype=np.int64)
+        st = np.asarray(status, dtype=np.int32)
+        self.n_pairs, self.status = (n, st) if batched else (int(n[0]), int(st[0]))
+
+
+def match_catalogs(cat1, cat2, max_sep=1.1, device_out=False, path=None):
+    """Cross-match two source catalogues by position on the device: the greedy
+    symmetric best match within ``max_sep`` pixels (``bsgp_match_catalogs``;
+    DESIGN §3.10, M1 to M6).  The candidates -- pairs with ``sqrt(dx^2 + dy^2)
+    <= max_sep`` -- are taken in the order of (squared distance, row of
+    catalogue 1, row of catalogue 2), a pair being accepted iff neither row is
+    taken.  With catalogue 1 the restored and catalogue 2 the original
+    catalogue and the default 1.1 this is the reference's published
+    ``results/*_MATCHED.csv``.
+
+    A catalogue is a :class:`SourceCatalog` (batched or not; one made with
+    ``device_out=True`` is matched from its device columns, no column is
+    copied), anything indexable by ``'xcentroid'`` / ``'ycentroid'`` (a dict, a
+    DataFrame, a table), an ``(x, y)`` tuple, or a list of those for a batch;
+    both sides must have one batch size.  A tuple is always one (x, y) pair, a
+    list always a batch.  Rows whose ``area`` is not > 0 (a SourceCatalog's
+    absent labels; any catalogue with that column) and rows with a non-finite
+    coordinate take no part.
+    ``path``: None / 'auto', 'lds' (both catalogues in LDS, at most
+    ``MATCH_LDS_MAX`` rows together) or 'global' (at most ``MATCH_MAX`` rows
+    each); the result does not depend on it.  Returns a :class:`CatalogMatch`."""
+    torch = _B.torch
+    (i1, b1), (i2, b2) = _match_items(cat1), _match_items(cat2)
+    if b1 != b2:
+        raise ValueError("one catalogue is a batch and the other is not")
+    sep, code = check_match_args(max_sep, path, len(i1), len(i2))
+    _B.require_gpu()
+    s1, s2 = _MatchSide(cat1), _MatchSide(cat2)
+    check_match_args(max_sep, path, s1.B, s2.B, s1.cap, s2.cap)
+    B = s1.B
+    m1 = torch.empty((B, s1.cap), dtype=torch.int32, device="cuda")
+    m2 = torch.empty((B, s2.cap), dtype=torch.int32, device="cuda")
+    sp = torch.empty((B, s1.cap), dtype=torch.float64, device="cuda")
+    npairs = torch.empty((B,), dtype=torch.int32, device="cuda")
+    st = torch.empty((B,), dtype=torch.int32, device="cuda")
+    _B.check(_B.lib().bsgp_match_catalogs(*s1.args(), *s2.args(), B, sep, code, _B._ptr(m1),
+                                          _B._ptr(m2), _B._ptr(sp), _B._ptr(npairs), _B._ptr(st),
+                                          _B.current_stream()))
+    m1h, m2h, sph, nph, sth = (t.cpu().numpy() for t in (m1, m2, sp, npairs, st))  # waits
+    out = CatalogMatch([m1h[b, :s1.n[b]] for b in range(B)], [m2h[b, :s2.n[b]] for b in range(B)],
+                       [sph[b, :s1.n[b]] for b in range(B)], sth, s1.labels, s2.labels, s1.batched)
+    if not np.array_equal(np.atleast_1d(out.n_pairs), nph):
+        raise _B.BsgpError(_B.BSGP_ERR_HIP, f"bsgp_match_catalogs reports {nph.tolist()} pairs, "
+                           f"match1 holds {np.atleast_1d(out.n_pairs).tolist()}")
+    if device_out:
+        out.match1_dev, out.match2_dev, out.sep1_dev = m1, m2, sp
+        out.n_pairs_dev, out.status_dev = npairs, st
+    return out
+
+
+def _one(match, cat1, cat2):
+    if match.batched or getattr(cat1, "batched", False) or getattr(cat2, "batched", False) \
+            or isinstance(cat1, list) or isinstance(cat2, list):
+        raise ValueError("one image at a time: pass the images of a batch one by one")
+
+
+def matched_columns(match, cat1, cat2, columns=None):
+    """The joined table of a match, in the layout of the reference's published
+    ``*_MATCHED.csv``: a dict of ``name_1`` for every column (the rows
+    ``match.idx1`` of ``cat1``), then ``name_2`` (the rows ``match.idx2`` of
+    ``cat2``), then ``Separation``.  ``columns``: the names (default: those of
+    ``cat1.to_dict()`` / ``cat1.keys()`` that ``cat2`` has too).  Host only;
+    the values are copied unchanged."""
+    _one(match, cat1, cat2)
+    if columns is None:
+        names = [list(c.to_dict()) if isinstance(c, SourceCatalog) else list(c.keys())
+                 for c in (cat1, cat2)]
+        columns = [k for k in names[0] if k in names[1]]
+    out = {}
+    for tag, cat, idx in (("_1", cat1, match.idx1), ("_2", cat2, match.idx2)):
+        for k in columns:
+            out[k + tag] = np.asarray(getattr(cat[k], "value", cat[k]))[idx]
+    out["Separation"] = np.asarray(match.separation)
+    return out
+
+
+def matched_metrics(orig, restored, max_sep=1.1, match=None):
+    """The per-star comparison of a restored with an original catalogue -- what
+    application_sgp_subdivisions.py:131-139 has commented out, because the two
+    catalogues differ in length and order.  ``restored`` is matched as
+    catalogue 1 and ``orig`` as catalogue 2, as in the reference's published
+    tables (``match``: a :class:`CatalogMatch` made that way, instead of
+    :func:`match_catalogs`).  Per pair, from the catalogues' columns on the
+    host: ``flux_fractional_difference = 1 - restored.segment_flux /
+    orig.segment_flux``, ``fwhm_ratio`` and ``ellipticity_ratio`` (restored over
+    original), ``separation``, ``orig_label``, ``restored_label`` (``None``
+    without a ``label`` column); ``median_flux_fractional_difference``,
+    ``median_fwhm_ratio``, ``median_ellipticity_ratio`` (NaN without a pair);
+    ``n_pairs``, ``n_orig``, ``n_restored``."""
+    if match is None:
+        match = match_catalogs(restored, orig, max_sep)
+    _one(match, restored, orig)
+    r, o = ({k: np.asarray(getattr(c[k], "value", c[k]), dtype=np.float64) for k in METRIC_COLUMNS}
+            for c in (restored, orig))
+    i, j = match.idx1, match.idx2
+    with np.errstate(invalid="ignore", divide="ignore"):
+        out = dict(flux_fractional_difference=1.0 - r["segment_flux"][i] / o["segment_flux"][j],
+                   fwhm_ratio=r["fwhm"][i] / o["fwhm"][j],
+                   ellipticity_ratio=r["ellipticity"][i] / o["ellipticity"][j])
+    for k in tuple(out):
+        out["median_" + k] = float(np.median(out[k])) if len(i) else float("nan")
+    out.update(separation=np.asarray(match.separation), orig_label=match.labels2,
+               restored_label=match.labels1, n_pairs=int(match.n_pairs),
+               n_orig=len(o["segment_flux"]), n_restored=len(r["segment_flux"]))
+    return out

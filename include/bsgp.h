@@ -557,6 +557,65 @@ int bsgp_deblend_sources_large(const double* data, const int32_t* labels, int32_
                                int32_t connectivity, int32_t lds_max_box, int32_t* labels_out,
                                int32_t* nlabels_out, int32_t* status_out, void* stream);
 
+/* Cross-match of two source catalogues: which source of
+ * catalogue 1 is which source of catalogue 2, by position.  This is what the
+ * reference's four published tables results/..._MATCHED.csv hold (catalogue 1
+ * the restored, catalogue 2 the original catalogue, max_sep = 1.1 pixels), and
+ * what the per-star lines of application_sgp_subdivisions.py:131-139 need.
+ *  M1 row r of image b takes part iff r < min(n[b], cap), its valid entry is
+ *     > 0 (when valid is given) and its x and y are finite.  A non-finite
+ *     coordinate on a row that passes the other two tests sets
+ *     BSGP_MATCH_NONFINITE; n[b] > cap sets BSGP_MATCH_OVER_CAP and the rows
+ *     beyond cap are ignored.
+ *  M2 dx = x1[i] - x2[j], dy = y1[i] - y2[j], d2 = dx * dx + dy * dy, sep =
+ *     sqrt(d2): float64, one rounding per operation, no fused multiply-add.
+ *     (i, j) is a candidate iff sep <= max_sep (inclusive); an infinite d2 is
+ *     never one.  Both catalogues' scans evaluate this expression.  (The
+ *     kernels compare d2 with the largest float64 whose square root is <=
+ *     max_sep, found on the host: sqrt is monotone, so the candidates are the
+ *     same.)
+ *  M3 candidates are strictly ordered by (d2, i, j), lexicographic.
+ *  M4 the result is the greedy symmetric best match: the candidates are walked
+ *     in M3's order and a pair is accepted iff neither row is taken.  The
+ *     kernels compute it in rounds: every untaken row of either catalogue picks
+ *     its best untaken candidate by M3 (from catalogue 2's side the key is
+ *     (d2, i)), mutual picks are accepted, and a round that accepts nothing
+ *     ends the loop.  A round accepts at least the smallest remaining
+ *     candidate, so there are at most min(n1, n2) accepting rounds.
+ *  M5 match1 [B][cap1] = j or -1, match2 [B][cap2] = i or -1, sep1 [B][cap1] =
+ *     sep or NaN, npairs [B], status [B] (BSGP_MATCH_* bits).  Rows that take
+ *     no part, and rows from n[b] to cap, get -1 / NaN.
+ *  M6 a batch gives every image what it gets alone; the results depend neither
+ *     on the launch shape nor on the path.  B == 0 is a no-op that follows no
+ *     pointer.  Asynchronous on stream.
+ * Element (b, r) of a column is ptr[(b * cap + r) * stride]: the catalogue
+ * bsgp_segment_catalog writes is matched in place with x = f64_cols + 3, y =
+ * f64_cols + 4, stride 8 and valid = int_cols, vstride 5 (area 0 marks the rows
+ * of absent labels, whose zero coordinates are no points); plain arrays have
+ * stride 1 and valid NULL.  n1 / n2: device int32 [B], or NULL for cap.
+ * One workgroup serves one image pair.  path: BSGP_MATCH_AUTO, BSGP_MATCH_LDS
+ * (coordinates and state in LDS: cap1 + cap2 <= BSGP_MATCH_LDS_MAX; the host
+ * sees the caps, not n, so the caps decide) or BSGP_MATCH_GLOBAL (the same
+ * algorithm on a stream-ordered global workspace: cap1, cap2 <=
+ * BSGP_MATCH_MAX).  AUTO takes the LDS path where it serves the caps.
+ * BSGP_ERR_UNSUPPORTED: a cap over BSGP_MATCH_MAX, or caps the chosen path does
+ * not serve.  BSGP_ERR_ARG: max_sep negative or not finite, a cap < 1, B < 0,
+ * a stride < 1, an unknown path, a NULL array other than valid1 / valid2 /
+ * n1 / n2. */
+#define BSGP_MATCH_LDS_MAX 4096
+#define BSGP_MATCH_MAX 16384
+#define BSGP_MATCH_AUTO 0
+#define BSGP_MATCH_LDS 1
+#define BSGP_MATCH_GLOBAL 2
+#define BSGP_MATCH_NONFINITE 1
+#define BSGP_MATCH_OVER_CAP 2
+int bsgp_match_catalogs(const double* x1, const double* y1, int32_t stride1, const int32_t* valid1,
+                        int32_t vstride1, int32_t cap1, const int32_t* n1, const double* x2,
+                        const double* y2, int32_t stride2, const int32_t* valid2, int32_t vstride2,
+                        int32_t cap2, const int32_t* n2, int32_t B, double max_sep, int32_t path,
+                        int32_t* match1_out, int32_t* match2_out, double* sep1_out,
+                        int32_t* npairs_out, int32_t* status_out, void* stream);
+
 /* Star-stamp metrics: what application_sgp_star_stamps.py:117-142
  * computes for the observed and the restored stamp.  All three are
  * asynchronous; every image, profile and pair is processed on its own and gets
