@@ -44,6 +44,11 @@ BSGP_MATCH_LDS_MAX = 4096  # cap1 + cap2 of the cross-match's LDS path (include/
 BSGP_MATCH_MAX = 16384  # rows of one catalogue in a cross-match
 BSGP_MATCH_AUTO, BSGP_MATCH_LDS, BSGP_MATCH_GLOBAL = 0, 1, 2
 BSGP_MATCH_NONFINITE, BSGP_MATCH_OVER_CAP = 1, 2
+# star-stamp status bits (include/bsgp.h): the cutout's, the driver's selection's, the choice's
+BSGP_STAMP_PARTIAL, BSGP_STAMP_NO_OVERLAP, BSGP_STAMP_BAD_POSITION = 1, 2, 4
+BSGP_STAMP_NO_SOURCE, BSGP_STAMP_MULTI_SOURCE, BSGP_STAMP_BAD_FLUX = 8, 16, 32
+BSGP_STAMP_NO_CANDIDATE, BSGP_STAMP_RESTORED_NO_SOURCE = 64, 128
+BSGP_STAMP_ROW_COLS = 11  # columns of a bsgp_stamp_select result row
 
 
 class BsgpError(RuntimeError):
@@ -189,6 +194,9 @@ def lib():
             L.bsgp_radial_profile.argtypes = [vp, i32, i32, i32, i32, vp, i32, vp, vp, vp]
             L.bsgp_fit_gauss1d.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]
             L.bsgp_wasserstein1.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp]
+            L.bsgp_extract_stamps.argtypes = [vp, i32, i32, i32, vp, i32, i32, i32, vp, vp, vp, vp]
+            L.bsgp_stamp_select.argtypes = [vp, vp, i32, vp, i32, vp, i32, i32, vp, vp, vp, vp,
+                                            vp, vp]
             for name in ["bsgp_plan_create", "bsgp_plan_create_checked", "bsgp_plan_destroy", "bsgp_plan_info",
                          "bsgp_solve_device", "bsgp_solve_host", "bsgp_solve_profiled",
                          "bsgp_apply_operator",
@@ -202,7 +210,7 @@ def lib():
                          "bsgp_plan_static_geo", "bsgp_radial_profile", "bsgp_fit_gauss1d",
                          "bsgp_wasserstein1", "bsgp_deblend_sources",
                          "bsgp_deblend_sources_large", "bsgp_segment_local_background",
-                         "bsgp_match_catalogs"]:
+                         "bsgp_match_catalogs", "bsgp_extract_stamps", "bsgp_stamp_select"]:
                 getattr(L, name).restype = ctypes.c_int
             if L.bsgp_abi_version() != ABI_VERSION:
                 raise BsgpError(-3, f"{LIB_PATH} has ABI {L.bsgp_abi_version()}, this binding "
@@ -220,7 +228,8 @@ EXPORTED = ["bsgp_plan_create", "bsgp_plan_create_checked", "bsgp_plan_destroy",
             "bsgp_convolve2d", "bsgp_detect_sources", "bsgp_segment_catalog",
             "bsgp_plan_set_static_geo", "bsgp_plan_static_geo", "bsgp_radial_profile",
             "bsgp_fit_gauss1d", "bsgp_wasserstein1", "bsgp_deblend_sources",
-            "bsgp_deblend_sources_large", "bsgp_segment_local_background", "bsgp_match_catalogs"]
+            "bsgp_deblend_sources_large", "bsgp_segment_local_background", "bsgp_match_catalogs",
+            "bsgp_extract_stamps", "bsgp_stamp_select"]
 
 
 def check(rc):

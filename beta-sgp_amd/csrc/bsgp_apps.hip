@@ -1,7 +1,8 @@
 // bsgp_apps.hip — the entry points of the C-ABI host layer that take no plan
 // (declared in include/bsgp.h): the projection, tiles, FITS pixels, PSF stamps,
 // sky background, convolution, detection, catalogue, local background,
-// deblending, catalogue cross-match, star-stamp metrics and the divergences.
+// deblending, catalogue cross-match, star-stamp metrics, cutouts and selection,
+// and the divergences.
 // Each validates its arguments and launches its kernels.
 #include <cmath>
 #include <cstdio>
@@ -491,6 +492,56 @@ int bsgp_wasserstein1(const double* u, const int32_t* ulen, const double* v, con
   a.P = 2;
   while (a.P < 2 * rcap) a.P *= 2;
   HIP_TRY(launch_stamp_w1(a, (hipStream_t)stream));
+  return BSGP_OK;
+}
+
+int bsgp_extract_stamps(const void* img, int32_t dtype, int32_t H, int32_t W, const double* xy,
+                        int32_t n, int32_t sh, int32_t sw, void* out, int32_t* box_out,
+                        int32_t* status_out, void* stream) {
+  if (n < 0) return fail(BSGP_ERR_ARG, "n must be >= 0");
+  if (dtype != BSGP_DTYPE_F32 && dtype != BSGP_DTYPE_F64)
+    return fail(BSGP_ERR_ARG, "dtype must be BSGP_DTYPE_F32 or BSGP_DTYPE_F64");
+  if (H < 1 || W < 1) return fail(BSGP_ERR_ARG, "H and W must be >= 1");
+  if (sh < 1 || sw < 1) return fail(BSGP_ERR_ARG, "the stamp size (sh, sw) must be >= 1");
+  if ((int64_t)sh * sw > kStampCutMaxPixels) {
+    char msg[128];
+    snprintf(msg, sizeof msg, "stamp of %lld pixels: a cutout holds at most %d",
+             (long long)sh * sw, kStampCutMaxPixels);
+    return fail(BSGP_ERR_UNSUPPORTED, msg);
+  }
+  if (n == 0) return BSGP_OK;
+  if (!img) return fail(BSGP_ERR_ARG, "img is NULL");
+  if (!xy) return fail(BSGP_ERR_ARG, "xy is NULL");
+  if (!out || !box_out || !status_out)
+    return fail(BSGP_ERR_ARG, "out / box_out / status_out is NULL");
+  StampCutArgs a{};
+  a.img = img, a.xy = xy, a.H = H, a.W = W, a.n = n, a.sh = sh, a.sw = sw;
+  a.out = out, a.box = box_out, a.status = status_out;
+  HIP_TRY(launch_extract_stamps(a, dtype == BSGP_DTYPE_F32, (hipStream_t)stream));
+  return BSGP_OK;
+}
+
+int bsgp_stamp_select(const int32_t* res_nlabels, const double* res_cols, int32_t res_stride,
+                      const double* obs_cols, int32_t obs_stride, const int32_t* iters, int32_t n,
+                      int32_t K, double* scores_out, int32_t* best_out, double* rows_out,
+                      int32_t* num_iters_out, int32_t* status_out, void* stream) {
+  if (n < 0) return fail(BSGP_ERR_ARG, "n must be >= 0");
+  if (K < 1) return fail(BSGP_ERR_ARG, "K must be >= 1");
+  if (res_stride < 8 || obs_stride < 8)
+    return fail(BSGP_ERR_ARG, "res_stride and obs_stride must be >= 8");
+  if ((int64_t)n * K > 0x7fffffff) return fail(BSGP_ERR_ARG, "n * K must be below 2^31");
+  if (n == 0) return BSGP_OK;
+  if (!res_nlabels || !res_cols || !obs_cols || !iters)
+    return fail(BSGP_ERR_ARG, "res_nlabels / res_cols / obs_cols / iters is NULL");
+  if (!scores_out || !best_out || !rows_out || !num_iters_out || !status_out)
+    return fail(BSGP_ERR_ARG,
+                "scores_out / best_out / rows_out / num_iters_out / status_out is NULL");
+  StampSelectArgs a{};
+  a.res_nlabels = res_nlabels, a.res_cols = res_cols, a.obs_cols = obs_cols, a.iters = iters;
+  a.n = n, a.K = K, a.res_stride = res_stride, a.obs_stride = obs_stride;
+  a.scores = scores_out, a.best = best_out, a.rows = rows_out, a.num_iters = num_iters_out;
+  a.status = status_out;
+  HIP_TRY(launch_stamp_select(a, (hipStream_t)stream));
   return BSGP_OK;
 }
 

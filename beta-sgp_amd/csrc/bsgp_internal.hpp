@@ -304,6 +304,32 @@ struct StampW1Args {
 hipError_t launch_stamp_radprof(const StampProfArgs& a, int f32, hipStream_t s);
 hipError_t launch_stamp_fit(const StampFitArgs& a, hipStream_t s);
 hipError_t launch_stamp_w1(const StampW1Args& a, hipStream_t s);
+// ---- star-stamp cutouts and selection (bsgp_starstamps.hip) ----
+constexpr int kStampCutMaxPixels = 1 << 24;  // sh * sw of one cutout (an int index per stamp)
+constexpr int kStampBoxLimit = 1 << 30;      // |imin| of a box: imin + size stays an int
+constexpr int kStampRowCols = BSGP_STAMP_ROW_COLS;
+struct StampCutArgs {
+  const void* img;   // [H][W] float32 or float64
+  const double* xy;  // [n][2]: (x, y) = (column, row)
+  int H, W, n, sh, sw;
+  void* out;    // [n][sh][sw] in the image's type
+  int* box;     // [n][4]: the untrimmed x0, y0, x1, y1
+  int* status;  // [n]: BSGP_STAMP_PARTIAL / NO_OVERLAP / BAD_POSITION
+};
+struct StampSelectArgs {
+  const int* res_nlabels;   // [n * K]
+  const double* res_cols;   // row of label 1 of restored image i at res_cols + i * res_stride
+  const double* obs_cols;   // row of label 1 of observed stamp s at obs_cols + s * obs_stride
+  const int* iters;         // [n * K]
+  int n, K, res_stride, obs_stride;
+  double* scores;  // [n][K]
+  int* best;       // [n]
+  double* rows;    // [n][kStampRowCols]
+  int* num_iters;  // [n]
+  int* status;     // [n]: BSGP_STAMP_NO_CANDIDATE / RESTORED_NO_SOURCE
+};
+hipError_t launch_extract_stamps(const StampCutArgs& a, int f32, hipStream_t s);
+hipError_t launch_stamp_select(const StampSelectArgs& a, hipStream_t s);
 struct PsfModel;
 hipError_t launch_psf_stamps(const PsfModel& m, const double* xy, int n, int spatial,
                              int normalize, double* out, hipStream_t s);

@@ -10,6 +10,14 @@ The reference computes them per star with numpy, astropy and scipy
 DESIGN §3.9) for one stamp or a batch; :func:`stamp_metrics` chains them for a
 batch without a host synchronisation in between.
 
+The application's loop around them (:56-148) is here as well:
+:func:`cutout_stamps` (``Cutout2D`` at float positions, ``bsgp_extract_stamps``),
+:func:`select_single_source` (the ``len(scat) == 1`` selection) and the driver
+:func:`sgp_star_stamps`, which chains the cutouts, the selection, ONE batched
+solve of every (star, candidate), the restored catalogue, the choice among the
+candidates on the device (``bsgp_stamp_select``) and the metrics (DESIGN
+§3.11).
+
 ``center`` is ``(c0, c1)`` with ``c0`` measured along the rows (axis 0), as
 the reference's ``np.indices`` order has it; the reference passes
 ``(xcentroid, ycentroid)`` there, and that quirk is kept: pass what the
@@ -21,6 +29,13 @@ import _bsgp as _B
 
 MAX_PIXELS = 16384  # H * W of one stamp
 MAX_BINS = 256      # radial bins, profile length, sample length
+CUT_MAX_PIXELS = 1 << 24  # sh * sw of one cutout
+BOX_LIMIT = 1 << 30       # |imin| of a cutout's box (include/bsgp.h)
+# columns of a bsgp_stamp_select result row
+ROW_COLUMNS = ("orig_flux", "restored_flux", "flux_fractional_difference", "fwhm_ratio",
+               "ellipticity_ratio", "orig_xcentroid", "orig_ycentroid", "orig_fwhm",
+               "restored_xcentroid", "restored_ycentroid", "restored_fwhm")
+assert len(ROW_COLUMNS) == _B.BSGP_STAMP_ROW_COLS
 
 
 def _shape_of(a):
@@ -292,3 +307,308 @@ def stamp_metrics(orig_sub, restored_sub, orig_center, restored_center, orig_fwh
            "ier": torch.stack((io[:, 0], ir[:, 0]), 1), "nfev": torch.stack((io[:, 1], ir[:, 1]), 1),
            "wd": wd}
     return out if device_out else _B.to_host(out)
+
+
+# ------------------------------------------------- cutouts, selection, driver
+def _stamp_size(size):
+    ok = (int, np.integer)
+    if isinstance(size, ok) and not isinstance(size, (bool, np.bool_)):
+        size = (size, size)
+    if not (isinstance(size, (tuple, list)) and len(size) == 2 and all(
+            isinstance(v, ok) and not isinstance(v, (bool, np.bool_)) for v in size)):
+        raise ValueError(f"size must be an int or a pair (ny, nx) of ints, got {size!r}")
+    sh, sw = int(size[0]), int(size[1])
+    if sh < 1 or sw < 1:
+        raise ValueError(f"size must be positive, got {size!r}")
+    if sh * sw > CUT_MAX_PIXELS:
+        raise ValueError(f"a cutout holds at most {CUT_MAX_PIXELS} pixels, got {sh} x {sw}")
+    return sh, sw
+
+
+def check_cutout_args(shape, positions, size):
+    """The argument checks of cutout_stamps (host only): returns ((H, W),
+    positions [n, 2] float64, (sh, sw)).  A non-finite coordinate is no error:
+    it gets a status bit."""
+    if len(shape) != 2 or 0 in shape:
+        raise ValueError(f"image must be [H, W], got shape {tuple(shape)}")
+    try:
+        p = np.asarray(positions, np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("positions must be numbers, [n, 2] in (x, y)") from None
+    if p.shape == (0,):  # an empty list
+        p = p.reshape(0, 2)
+    if p.ndim != 2 or p.shape[1] != 2:
+        raise ValueError(f"positions must be [n, 2] in (x, y), got shape {p.shape}")
+    return (int(shape[0]), int(shape[1])), np.ascontiguousarray(p), _stamp_size(size)
+
+
+def cutout_stamps(image, positions, size=31, device_out=False):
+    """``Cutout2D(image, (x, y), size)`` (mode 'trim') at every row of
+    ``positions`` [n, 2] in ``(x, y)``, x the column
+    (application_sgp_star_stamps.py:58): ``bsgp_extract_stamps``, one launch.
+    ``image``: 2-D float32 or float64 (kept, so that a float32 frame keeps the
+    reference's float32 arithmetic) or integer (widened to float64), numpy or
+    CUDA tensor.  ``size``: an int or ``(ny, nx)``.  The box is astropy 4.3.1's:
+    per axis it starts at ``ceil(pos - size / 2)``.  Returns ``(stamps
+    [n, ny, nx], boxes [n, 4], status [n])``: the untrimmed ``x0, y0, x1, y1``
+    and 0 or one of ``BSGP_STAMP_PARTIAL`` (the box leaves the image; the pixels
+    outside are 0 -- the reference drops such a stamp), ``BSGP_STAMP_NO_OVERLAP``
+    (astropy raises; all 0) and ``BSGP_STAMP_BAD_POSITION`` (a non-finite
+    coordinate; all 0).  numpy arrays, or CUDA tensors with ``device_out=True``."""
+    (H, W), pos, (sh, sw) = check_cutout_args(_shape_of(image), _host(positions), size)
+    _B.require_gpu()
+    torch = _B.torch
+    img = _images(image)[0]
+    n = len(pos)
+    out = torch.empty((n, sh, sw), dtype=img.dtype, device="cuda")
+    box = torch.empty((n, 4), dtype=torch.int32, device="cuda")
+    st = torch.empty((n,), dtype=torch.int32, device="cuda")
+    if n:
+        xy = _dev_f64(pos, (n, 2))
+        dtype = _B.BSGP_DTYPE_F32 if img.dtype == torch.float32 else _B.BSGP_DTYPE_F64
+        _B.check(_B.lib().bsgp_extract_stamps(_B._ptr(img), dtype, H, W, _B._ptr(xy), n, sh, sw,
+                                              _B._ptr(out), _B._ptr(box), _B._ptr(st),
+                                              _B.current_stream()))
+    if device_out:
+        return out, box, st
+    res = _B.to_host({"s": out, "b": box, "t": st})
+    return res["s"], res["b"], res["t"]
+
+
+def select_single_source(stamps, box_size=(5, 5), n_pixels=5, localbkg_width=5, deblend=True):
+    """The application's selection (application_sgp_star_stamps.py:63-66): one
+    batched ``source_info`` over ``stamps`` [B, H, W] and the mask of the
+    stamps whose catalogue holds exactly one source.  The defaults are
+    ``utils.source_info``'s own (restoration/utils.py:219, 235, 245: 5 x 5
+    boxes, 5 pixels, ``SourceFinder(deblend=True)``, ``localbkg_width=5``).  The
+    application's call ``source_info(cutout.data, localbkg_width=5)`` is stale
+    against that signature (it takes no such keyword); what it means is
+    what the function does anyway.  Returns ``(catalog, background, mask)``, the
+    first two as ``segmentation.source_info(..., device_out=True)`` returns
+    them, ``mask = catalog.nlabels == 1`` on the host."""
+    import segmentation
+    if len(_shape_of(stamps)) != 3:
+        raise ValueError(f"stamps must be a batch [B, H, W], got shape {_shape_of(stamps)}")
+    cat, bkg = segmentation.source_info(stamps, box_size, n_pixels, device_out=True,
+                                        deblend=deblend, localbkg_width=localbkg_width)
+    return cat, bkg, np.asarray(cat.nlabels) == 1
+
+
+def _select_dev(nlabels, res_cols, obs_cols, iters, n, K):
+    """bsgp_stamp_select on device tensors: res_cols [n * K, cap, 8], obs_cols
+    [n, cap, 8], nlabels and iters int32 [n * K]."""
+    torch = _B.torch
+    scores = torch.empty((n, K), dtype=torch.float64, device="cuda")
+    rows = torch.empty((n, _B.BSGP_STAMP_ROW_COLS), dtype=torch.float64, device="cuda")
+    best, nit, st = (torch.empty((n,), dtype=torch.int32, device="cuda") for _ in range(3))
+    _B.check(_B.lib().bsgp_stamp_select(
+        _B._ptr(nlabels), _B._ptr(res_cols), res_cols.shape[1] * 8, _B._ptr(obs_cols),
+        obs_cols.shape[1] * 8, _B._ptr(iters), n, K, _B._ptr(scores), _B._ptr(best), _B._ptr(rows),
+        _B._ptr(nit), _B._ptr(st), _B.current_stream()))
+    return scores, best, rows, nit, st
+
+
+def stamp_select(res_nlabels, res_cols, obs_cols, iters, K, device_out=False):
+    """The choice among the K restorations of each star and its result row
+    (application_sgp_star_stamps.py:92-98, 125-139; ``bsgp_stamp_select``).
+    Image ``s * K + k`` is candidate k of star s.  ``res_nlabels`` [n * K] and
+    ``res_cols`` [n * K, cap, 8]: the detections and the ``f64_cols`` of the
+    restored catalogue; ``obs_cols`` [n, cap, 8]: those of the observed one (row
+    0, label 1, is read); ``iters`` [n * K].  Returns ``(scores [n, K], best [n],
+    rows [n, 11], num_iters [n], status [n])``: ``best`` is
+    ``sgp.argmin_strict`` of the star's scores (-1 for its None), ``rows`` has
+    the columns ``ROW_COLUMNS``."""
+    torch = _B.torch
+    n = int(_shape_of(obs_cols)[0])
+    if K < 1 or _shape_of(res_cols)[:1] != (n * K,) or _shape_of(res_cols)[2:] != (8,) \
+            or _shape_of(obs_cols)[2:] != (8,) or len(_shape_of(res_cols)) != 3:
+        raise ValueError(f"res_cols must be [n * K, cap, 8] and obs_cols [n, cap, 8] for K = {K}, "
+                         f"got shapes {_shape_of(res_cols)} and {_shape_of(obs_cols)}")
+    if _shape_of(res_nlabels) != (n * K,) or _shape_of(iters) != (n * K,):
+        raise ValueError(f"res_nlabels and iters must be [n * K] = [{n * K}]")
+    _B.require_gpu()
+    out = _select_dev(_dev_i32(res_nlabels, n * K), _dev_f64(res_cols), _dev_f64(obs_cols),
+                      _dev_i32(iters, n * K), n, K)
+    if device_out:
+        return out
+    res = _B.to_host(dict(enumerate(out)))
+    return tuple(res[i] for i in range(5))
+
+
+RESULT_KEYS = ("ORIG_FLUX", "RESTORED_FLUX", "FLUX_FRACTIONAL_DIFFERENCE", "FWHM_RATIO",
+               "ELLIPTICITY_RATIO", "WD_RADIAL_PROFILE_DISTANCE", "NUM_ITERS", "EXEC_TIME")
+
+
+def star_stamp_kwargs(use_betadiv=True):
+    """The keywords of the application's solver calls
+    (application_sgp_star_stamps.py:82-89 and 107-112): DEFAULT_PARAMS unpacked
+    (:23), flux projection, start from the data, stop rule 3, saturation at
+    65000, scaled data, the circular A; for sgp_betaDiv also the adaptive beta
+    with its scheduled learning rate."""
+    import sgp
+    max_projs, gamma, beta, alpha_min, alpha_max, alpha, M_alpha, tau, M = sgp.DEFAULT_PARAMS
+    kw = dict(gamma=gamma, beta=beta, alpha_min=alpha_min, alpha_max=alpha_max, alpha=alpha,
+              M_alpha=M_alpha, tau=tau, M=M, max_projs=max_projs, proj_type=1, init_recon=2,
+              stop_criterion=3, ccd_sat_level=65000, scale_data=True,
+              use_original_SGP_Afunction=True)
+    if use_betadiv:
+        kw.update(lr=1e-3, lr_exp_param=0.1, schedule_lr=True, adapt_beta=True)
+    return kw
+
+
+def _empty_result(status, K, shape, device_out):
+    torch = _B.torch
+
+    def arr(shp, dt):
+        if device_out:
+            return torch.empty(shp, dtype=getattr(torch, np.dtype(dt).name), device="cuda")
+        return np.empty(shp, dt)
+
+    res = {k: arr((0,), np.float64) for k in RESULT_KEYS}
+    res["NUM_ITERS"] = arr((0,), np.int32)
+    res.update(kept=np.empty((0,), np.int64), status=status, best=arr((0,), np.int32),
+               best_beta=np.empty((0,), np.float64), scores=arr((0, K), np.float64),
+               beta_final=arr((0,), np.float64), x=arr((0,) + tuple(shape), np.float64),
+               solver_status=arr((0, K), np.int64), metrics=None)
+    return res
+
+
+def sgp_star_stamps(image, positions, psf, size=31, use_betadiv=True, betas=None, MAXIT=500,
+                    device_out=False, **sgp_kwargs):
+    """The star-stamp application's loop (application_sgp_star_stamps.py:56-148)
+    for one frame and a list of star coordinates ``positions`` [n, 2] in
+    ``(x, y)``, with every star's work batched:
+
+    1. :func:`cutout_stamps`; a stamp with a non-zero status is dropped (:60-61).
+    2. :func:`select_single_source`; kept are the stamps with exactly one source
+       (:65-66) whose ``segment_flux[0]`` is positive (the reference raises on
+       another: no positive entry in flux / (flux + bkg) * AT(gn); here it is the
+       status bit ``BSGP_STAMP_BAD_FLUX``).
+    3. ONE batched solve of (kept stamp x candidate) with ``bkg =
+       background_median`` and ``flux = segment_flux[0]`` of the stamp and
+       :func:`star_stamp_kwargs`; ``sgp_kwargs`` override those and pass anything
+       else ``sgp_betaDiv_batch`` / ``sgp_batch`` take.  The candidates are
+       ``betas`` (default ``sgp.app_beta_candidates()``, :69-75);
+       ``use_betadiv=False`` is the ``sgp(...)`` branch (:107-112) with one
+       candidate.
+    4. One batched ``source_info`` of all restored candidates (:90, 114).
+    5. ``bsgp_stamp_select``: the scores, the winner (:95-97) and the result row
+       of every star on the device; no host round trip decides it.
+    6. :func:`stamp_metrics` on the winners' background-subtracted stamps (the
+       catalogues' ``data``, gathered by ``best`` on the device).
+
+    The application's final solve (:98-105) repeats the best candidate's run
+    exactly, so it is not run again (as in ``sgp.sgp_betaDiv_multistart``).
+    The host reads the cutout status and the catalogues (``source_info`` returns
+    its columns on the host) before the solve, to size the batch; after the solve
+    only ``stamp_metrics`` reads the winners' centres and widths back, to size
+    its profiles.
+
+    Returns a dict.  One entry per kept star, in input order: ``ORIG_FLUX``,
+    ``RESTORED_FLUX``, ``FLUX_FRACTIONAL_DIFFERENCE``, ``FWHM_RATIO``,
+    ``ELLIPTICITY_RATIO``, ``WD_RADIAL_PROFILE_DISTANCE``, ``NUM_ITERS`` (the
+    arrays the reference saves), ``best`` (-1: none), ``best_beta``, ``scores``
+    [n_kept, K], ``beta_final`` (of the winner; NaN for ``use_betadiv=False``),
+    ``x`` (the winners' restored stamps), ``solver_status`` [n_kept, K] (the
+    solver's status bits, ``_bsgp.check_status``) and ``metrics`` (the
+    :func:`stamp_metrics` dict).  ``EXEC_TIME`` is NOT per star: it is the time
+    of the one batched solve (device events around it) divided evenly over the
+    kept stars.  ``kept``: their indices into ``positions``.  ``status`` [n]: 0
+    for a kept star with a result, else the cutout's bit or one of
+    ``BSGP_STAMP_NO_SOURCE``, ``_MULTI_SOURCE``, ``_BAD_FLUX`` (dropped),
+    ``_NO_CANDIDATE`` (no candidate's restoration has a detection) and
+    ``_RESTORED_NO_SOURCE`` (``use_betadiv=False``: the restoration has none): a
+    star with one of the last two keeps its row, with NaN for the restored flux,
+    the ratios and the distance and -1 iterations.  One star never makes the
+    driver raise; no position, or none that survives, returns empty arrays (and
+    ``metrics`` None) without a solve.  numpy arrays, or CUDA tensors with
+    ``device_out=True`` (``kept``, ``status`` and ``best_beta`` stay numpy)."""
+    import sgp
+    torch = _B.torch
+    (H, W), pos, (sh, sw) = check_cutout_args(_shape_of(image), _host(positions), size)
+    betas = [float(b) for b in (sgp.app_beta_candidates() if betas is None else betas)] \
+        if use_betadiv else [float("nan")]
+    K = len(betas)
+    if K < 1:
+        raise ValueError("betas must hold at least one candidate")
+    _B.require_gpu()
+    n = len(pos)
+    if n == 0:
+        return _empty_result(np.zeros(0, np.int32), K, (sh, sw), device_out)
+    stamps, _, st = cutout_stamps(image, pos, (sh, sw), device_out=True)
+    status = st.cpu().numpy().astype(np.int32)
+    full = np.flatnonzero(status == 0)
+    if full.size == 0:
+        return _empty_result(status, K, (sh, sw), device_out)
+    cat_o, bkg_o, single = select_single_source(stamps[torch.from_numpy(full).to("cuda")])
+    nlab = np.asarray(cat_o.nlabels)
+    flux = np.array([f[0] if len(f) else np.nan for f in cat_o.segment_flux], np.float64)
+    status[full[nlab == 0]] |= _B.BSGP_STAMP_NO_SOURCE
+    status[full[nlab > 1]] |= _B.BSGP_STAMP_MULTI_SOURCE
+    keep = single & (flux > 0)
+    status[full[single & ~keep]] |= _B.BSGP_STAMP_BAD_FLUX
+    kept = full[keep]
+    nk = int(kept.size)
+    if nk == 0:
+        return _empty_result(status, K, (sh, sw), device_out)
+    kk = torch.from_numpy(np.flatnonzero(keep)).to("cuda")
+    gns = stamps[torch.from_numpy(kept).to("cuda")].repeat_interleave(K, dim=0)
+    kw = star_stamp_kwargs(use_betadiv)
+    kw.update(sgp_kwargs)
+    kw.update(MAXIT=MAXIT, device_out=True,
+              flux=np.repeat(flux[keep], K))
+    bkgs = np.repeat(np.asarray(bkg_o.background_median, np.float64)[keep], K)
+    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0.record()
+    if use_betadiv:
+        out = sgp.sgp_betaDiv_batch(gns, psf, bkgs, betaParams=np.tile(betas, nk), **kw)
+    else:
+        out = sgp.sgp_batch(gns, psf, bkgs, **kw)
+    t1.record()
+    # a restoration with a non-finite pixel (source_info refuses those) counts
+    # as one without a detection: it is catalogued as an empty image
+    xr = out["x"]
+    xr = torch.where(torch.isfinite(xr).reshape(nk * K, -1).all(dim=1)[:, None, None], xr,
+                     torch.zeros_like(xr))
+    cat_r, _, _ = select_single_source(xr)
+    nlab_r = torch.from_numpy(np.ascontiguousarray(cat_r.nlabels, np.int32)).to("cuda")
+    scores, best, rows, nit, sel = _select_dev(nlab_r, cat_r.f64_cols,
+                                               cat_o.f64_cols[kk].contiguous(), out["iters"], nk, K)
+    # the winner's image index (candidate 0 stands in where there is none: its
+    # results are overwritten with NaN below)
+    win = torch.arange(nk, device="cuda") * K + best.clamp(min=0).to(torch.int64)
+    none = sel != 0
+    rows_h = rows.cpu().numpy()  # the centres and widths size the profiles
+    co, fo, cr, fr = rows_h[:, 5:7], rows_h[:, 7], rows_h[:, 8:10], rows_h[:, 10]
+    with np.errstate(invalid="ignore"):
+        bad = ~(np.isfinite(rows_h[:, 5:]).all(axis=1) & (fo > 0) & (fr > 0))
+        bad |= ~(profile_reach((sh, sw), np.where(bad[:, None], 0.0, co)) < MAX_BINS)
+        bad |= ~(profile_reach((sh, sw), np.where(bad[:, None], 0.0, cr)) < MAX_BINS)
+    # a star without a winner, or with a centre or width no profile can be made
+    # from, is measured about (0, 0) with width 1 and its distance set to NaN
+    met = stamp_metrics(cat_o.data[kk], cat_r.data[win], np.where(bad[:, None], 0.0, co),
+                        np.where(bad[:, None], 0.0, cr), np.where(bad, 1.0, fo),
+                        np.where(bad, 1.0, fr), device_out=True)
+    nan = float("nan")
+    badd = torch.from_numpy(bad).to("cuda") | none
+    for k in ("restored_radprof", "fitted_restored", "wd"):
+        met[k] = met[k].masked_fill(badd.reshape((-1,) + (1,) * (met[k].dim() - 1)), nan)
+    t1.synchronize()
+    sel_h = sel.cpu().numpy()
+    status[kept] |= sel_h
+    best_h = best.cpu().numpy()
+    res = {nm: rows[:, j] for j, nm in enumerate(RESULT_KEYS[:5])}
+    res.update(WD_RADIAL_PROFILE_DISTANCE=met["wd"], NUM_ITERS=nit,
+               EXEC_TIME=torch.full((nk,), t0.elapsed_time(t1) * 1e-3 / nk, dtype=torch.float64,
+                                    device="cuda"),
+               best=best, scores=scores,
+               beta_final=out["beta_final"][win].masked_fill(none, nan) if use_betadiv
+               else torch.full((nk,), nan, dtype=torch.float64, device="cuda"),
+               x=out["x"][win].masked_fill(none[:, None, None], nan),
+               solver_status=out["counters"][:, 3].reshape(nk, K))
+    if not device_out:
+        res = _B.to_host(res)
+        met = _B.to_host(met)
+    res.update(kept=kept, status=status, metrics=met,
+               best_beta=np.where(best_h >= 0, np.asarray(betas)[np.maximum(best_h, 0)], np.nan))
+    return res

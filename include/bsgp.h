@@ -659,6 +659,73 @@ int bsgp_fit_gauss1d(const double* prof, const int32_t* len, int32_t B, int32_t 
 int bsgp_wasserstein1(const double* u, const int32_t* ulen, const double* v, const int32_t* vlen,
                       int32_t B, int32_t rcap, double* out, void* stream);
 
+/* Star-stamp cutouts and selection: the two ends of
+ * application_sgp_star_stamps.py's loop around the solver and the metrics.
+ * Both are asynchronous; n == 0 is a no-op that follows no pointer.
+ *
+ * bsgp_extract_stamps: Cutout2D(img, (x, y), size=(sh, sw)) in its default
+ * mode 'trim' (application_sgp_star_stamps.py:58) for n positions xy [n][2]
+ * (device float64; x the column, y the row).  The box is astropy 4.3.1's
+ * overlap_slices: per axis imin = (int)ceil(pos - size / 2.0) in float64 and
+ * imax = imin + size (imin is kept inside +-2^30; such a box overlaps no
+ * image).  img: device [H][W], float32 or float64 (dtype = BSGP_DTYPE_*); out
+ * [n][sh][sw] keeps that type and the values bit for bit.  box_out: int32
+ * [n][4] = the untrimmed x0, y0, x1, y1 (exclusive ends).  status_out: int32
+ * [n], 0 for a stamp that lies inside the image (touching the border
+ * included), else one of
+ *   BSGP_STAMP_PARTIAL       the box leaves the image: the pixels outside are 0
+ *                            (the reference drops the stamp: its trimmed
+ *                            cutout's shape is not (31, 31), :60-61)
+ *   BSGP_STAMP_NO_OVERLAP    the box misses the image (astropy raises
+ *                            NoOverlapError): the stamp is all 0
+ *   BSGP_STAMP_BAD_POSITION  a coordinate is not finite (astropy raises
+ *                            ValueError): the stamp and the box are all 0
+ * BSGP_ERR_ARG: a NULL array, an unknown dtype, H, W, sh or sw < 1, n < 0;
+ * BSGP_ERR_UNSUPPORTED: sh * sw > 2^24. */
+#define BSGP_STAMP_PARTIAL 1
+#define BSGP_STAMP_NO_OVERLAP 2
+#define BSGP_STAMP_BAD_POSITION 4
+int bsgp_extract_stamps(const void* img, int32_t dtype, int32_t H, int32_t W, const double* xy,
+                        int32_t n, int32_t sh, int32_t sw, void* out, int32_t* box_out,
+                        int32_t* status_out, void* stream);
+/* bsgp_stamp_select: the choice among the K restorations of each of n stars and
+ * the star's result row (application_sgp_star_stamps.py:92-98 and 125-139).
+ * Image i = s * K + k is candidate k of star s.  res_nlabels [n * K]: the
+ * detections of restored image i; res_cols + i * res_stride: the f64_cols row
+ * of its label 1 (the reference reads element [0] of every column), as
+ * bsgp_segment_catalog writes it; obs_cols + s * obs_stride: that row of the
+ * observed stamp; iters [n * K]: the solver's iterations.  Strides count
+ * float64 values and are at least 8.
+ *   scores_out [n][K] = 1 - flux_r / flux_o, or +inf where res_nlabels <= 0
+ *   best_out [n]      the reference's running minimum from +inf with a strict
+ *                     comparison: the first of equal scores wins, NaN never
+ *                     does; -1 when no score is below +inf (status
+ *                     BSGP_STAMP_NO_CANDIDATE).  K == 1 is the sgp(...) branch
+ *                     (:107-112): no search, best = 0, and a restoration
+ *                     without a detection sets BSGP_STAMP_RESTORED_NO_SOURCE
+ *   rows_out [n][BSGP_STAMP_ROW_COLS] = orig_flux, restored_flux,
+ *                     flux_fractional_difference, fwhm_ratio, ellipticity_ratio,
+ *                     then (xcentroid, ycentroid, fwhm) of the observed stamp and
+ *                     of the winner; with a status bit the winner's entries are
+ *                     NaN
+ *   num_iters_out [n] iters of the winner, or -1
+ *   status_out [n]    0 or one of the two bits
+ * fwhm and ellipticity come from covar_sigx2 / sigxy / sigy2 by the formulas of
+ * photutils' documentation, one rounding per operation and no fused
+ * multiply-add.  The other BSGP_STAMP_* bits belong to the driver's selection
+ * (no, several sources; a non-positive flux) and are set on the host.
+ * BSGP_ERR_ARG: a NULL array, n < 0, K < 1, a stride < 8. */
+#define BSGP_STAMP_NO_SOURCE 8
+#define BSGP_STAMP_MULTI_SOURCE 16
+#define BSGP_STAMP_BAD_FLUX 32
+#define BSGP_STAMP_NO_CANDIDATE 64
+#define BSGP_STAMP_RESTORED_NO_SOURCE 128
+#define BSGP_STAMP_ROW_COLS 11
+int bsgp_stamp_select(const int32_t* res_nlabels, const double* res_cols, int32_t res_stride,
+                      const double* obs_cols, int32_t obs_stride, const int32_t* iters, int32_t n,
+                      int32_t K, double* scores_out, int32_t* best_out, double* rows_out,
+                      int32_t* num_iters_out, int32_t* status_out, void* stream);
+
 int bsgp_device_synchronize(void);
 const char* bsgp_last_error(void);
 /* The persistent solver's compile-time-geometry path (256 x 256 images on a
