@@ -49,6 +49,8 @@ BSGP_STAMP_PARTIAL, BSGP_STAMP_NO_OVERLAP, BSGP_STAMP_BAD_POSITION = 1, 2, 4
 BSGP_STAMP_NO_SOURCE, BSGP_STAMP_MULTI_SOURCE, BSGP_STAMP_BAD_FLUX = 8, 16, 32
 BSGP_STAMP_NO_CANDIDATE, BSGP_STAMP_RESTORED_NO_SOURCE = 64, 128
 BSGP_STAMP_ROW_COLS = 11  # columns of a bsgp_stamp_select result row
+# status bits of the background-matched co-add (include/bsgp.h)
+BSGP_COADD_NONFINITE, BSGP_COADD_ISOLATED, BSGP_COADD_NOT_CONVERGED = 1, 2, 4
 
 
 class BsgpError(RuntimeError):
@@ -167,6 +169,10 @@ def lib():
             L.bsgp_beta_div_grad_parts.argtypes = [i64, vp, vp, dbl, vp, vp, vp]
             L.bsgp_extract_tiles.argtypes = [vp, i32, i32, vp, i32, i32, i32, vp, vp]
             L.bsgp_coadd_tiles.argtypes = [vp, i32, i32, i32, vp, i32, i32, vp, vp, vp]
+            L.bsgp_tile_offsets.argtypes = [vp, i32, i32, i32, vp, vp, i32, vp, vp, vp]
+            L.bsgp_tile_corrections.argtypes = [i32, vp, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp,
+                                                vp]
+            L.bsgp_coadd_tiles_matched.argtypes = [vp, i32, i32, i32, vp, vp, i32, i32, vp, vp, vp]
             L.bsgp_fits_to_f64.argtypes = [vp, i64, i32, dbl, dbl, vp, vp]
             L.bsgp_psf_stamps.argtypes = [ctypes.POINTER(PsfModel), vp, i32, i32, i32, vp, vp]
             L.bsgp_plan_set_psfs.argtypes = [vp, vp, i32, vp]
@@ -210,7 +216,9 @@ def lib():
                          "bsgp_plan_static_geo", "bsgp_radial_profile", "bsgp_fit_gauss1d",
                          "bsgp_wasserstein1", "bsgp_deblend_sources",
                          "bsgp_deblend_sources_large", "bsgp_segment_local_background",
-                         "bsgp_match_catalogs", "bsgp_extract_stamps", "bsgp_stamp_select"]:
+                         "bsgp_match_catalogs", "bsgp_extract_stamps", "bsgp_stamp_select",
+                         "bsgp_tile_offsets", "bsgp_tile_corrections",
+                         "bsgp_coadd_tiles_matched"]:
                 getattr(L, name).restype = ctypes.c_int
             if L.bsgp_abi_version() != ABI_VERSION:
                 raise BsgpError(-3, f"{LIB_PATH} has ABI {L.bsgp_abi_version()}, this binding "
@@ -229,7 +237,8 @@ EXPORTED = ["bsgp_plan_create", "bsgp_plan_create_checked", "bsgp_plan_destroy",
             "bsgp_plan_set_static_geo", "bsgp_plan_static_geo", "bsgp_radial_profile",
             "bsgp_fit_gauss1d", "bsgp_wasserstein1", "bsgp_deblend_sources",
             "bsgp_deblend_sources_large", "bsgp_segment_local_background", "bsgp_match_catalogs",
-            "bsgp_extract_stamps", "bsgp_stamp_select"]
+            "bsgp_extract_stamps", "bsgp_stamp_select", "bsgp_tile_offsets",
+            "bsgp_tile_corrections", "bsgp_coadd_tiles_matched"]
 
 
 def check(rc):

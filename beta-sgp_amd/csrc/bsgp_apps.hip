@@ -1,5 +1,6 @@
 // bsgp_apps.hip — the entry points of the C-ABI host layer that take no plan
-// (declared in include/bsgp.h): the projection, tiles, FITS pixels, PSF stamps,
+// (declared in include/bsgp.h): the projection, tiles and their background-matched
+// co-add, FITS pixels, PSF stamps,
 // sky background, convolution, detection, catalogue, local background,
 // deblending, catalogue cross-match, star-stamp metrics, cutouts and selection,
 // and the divergences.
@@ -43,6 +44,66 @@ int bsgp_coadd_tiles(const double* tiles, int32_t n, int32_t th, int32_t tw, con
   if (!tiles || !boxes || !mean || H < 1 || W < 1 || n < 1 || n > 8192 || th < 1 || tw < 1)
     return fail(BSGP_ERR_ARG, "bad arguments");
   HIP_TRY(launch_coadd_tiles(tiles, n, th, tw, boxes, H, W, mean, footprint, (hipStream_t)stream));
+  return BSGP_OK;
+}
+
+int bsgp_tile_offsets(const double* tiles, int32_t n, int32_t th, int32_t tw, const int32_t* boxes,
+                      const int32_t* pairs, int32_t npairs, double* offsets, int32_t* status,
+                      void* stream) {
+  if (n < 1 || n > 8192 || th < 1 || tw < 1 || npairs < 0)
+    return fail(BSGP_ERR_ARG, "bad arguments");
+  if ((int64_t)th * tw > 0x7fffffffLL)
+    return fail(BSGP_ERR_UNSUPPORTED, "a tile holds fewer than 2^31 pixels (th * tw < 2^31)");
+  if (!tiles || !boxes || !status) return fail(BSGP_ERR_ARG, "tiles / boxes / status is NULL");
+  if (npairs > 0 && (!pairs || !offsets)) return fail(BSGP_ERR_ARG, "pairs / offsets is NULL");
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(hipMemsetAsync(status, 0, (size_t)n * sizeof(int), s));
+  if (npairs == 0) return BSGP_OK;
+  CoaddOffsetArgs a{};
+  a.tiles = tiles, a.boxes = boxes, a.pairs = pairs;
+  a.n = n, a.th = th, a.tw = tw, a.npairs = npairs;
+  a.offsets = offsets, a.status = status;
+  HIP_TRY(launch_pair_offsets(a, s));
+  return BSGP_OK;
+}
+
+int bsgp_tile_corrections(int32_t n, const int32_t* row_ptr, const int32_t* nbr,
+                          const int32_t* nbr_pair, const int32_t* nbr_sign,
+                          const int32_t* component, int32_t ncomp, const double* offsets,
+                          int32_t background_reference, double* corrections, int32_t* status,
+                          double* solve_info, void* stream) {
+  if (n < 1 || n > 8192 || ncomp < 1 || ncomp > n) return fail(BSGP_ERR_ARG, "bad arguments");
+  if (background_reference >= n)
+    return fail(BSGP_ERR_ARG, "background_reference must be a tile index (or < 0 for none)");
+  // (nbr, nbr_pair, nbr_sign and offsets are empty, and may be NULL, when no tile has a pair)
+  if (!row_ptr || !component || !corrections || !status)
+    return fail(BSGP_ERR_ARG, "row_ptr / component / corrections / status is NULL");
+  CoaddSolveArgs a{};
+  a.n = n, a.ncomp = ncomp, a.bref = background_reference < 0 ? -1 : background_reference;
+  a.row_ptr = row_ptr, a.nbr = nbr, a.nbr_pair = nbr_pair, a.nbr_sign = nbr_sign;
+  a.component = component, a.offsets = offsets;
+  a.c = corrections, a.status = status, a.info = solve_info;
+  hipStream_t s = (hipStream_t)stream;
+  // stream-ordered workspace: the call stays asynchronous
+  void* w = nullptr;
+  HIP_TRY(hipMallocAsync(&w, 2 * (size_t)n * sizeof(double), s));
+  a.ws = static_cast<double*>(w);
+  const hipError_t e = launch_solve_corrections(a, s);
+  const hipError_t ef = hipFreeAsync(w, s);
+  if (e != hipSuccess)
+    return fail(BSGP_ERR_HIP, std::string("corrections launch: ") + hipGetErrorString(e));
+  HIP_TRY(ef);
+  return BSGP_OK;
+}
+
+int bsgp_coadd_tiles_matched(const double* tiles, int32_t n, int32_t th, int32_t tw,
+                             const int32_t* boxes, const double* corrections, int32_t H, int32_t W,
+                             double* mean, double* footprint, void* stream) {
+  if (!tiles || !boxes || !corrections || !mean || H < 1 || W < 1 || n < 1 || n > 8192 ||
+      th < 1 || tw < 1)
+    return fail(BSGP_ERR_ARG, "bad arguments");
+  HIP_TRY(launch_coadd_tiles_matched(tiles, n, th, tw, boxes, corrections, H, W, mean, footprint,
+                                     (hipStream_t)stream));
   return BSGP_OK;
 }
 

@@ -150,6 +150,35 @@ hipError_t launch_coadd_tiles(const double* tiles, int n, int th, int tw, const 
                               int W, double* mean, double* footprint, hipStream_t s);
 hipError_t launch_fits_to_f64(const void* raw, int64_t n, int bitpix, double bscale, double bzero,
                               double* out, hipStream_t s);
+// ---- background-matched co-add (bsgp_coadd.hip) ------
+// relative residual |b - L c| / |b| at which the conjugate gradients stop (the recurrence's
+// residual; the corrections then sit within cond(L) * this of the solution: 1e-13 * 30 on
+// the tile grids of the application, under the 1e-10 at which reproject's solver stops)
+constexpr double kCoaddRtol = 1e-13;
+constexpr int kCoaddLdsMax = 160 * 1024 - 256;  // dynamic LDS of the matched co-add
+struct CoaddOffsetArgs {
+  const double* tiles;  // [n][th][tw]
+  const int* boxes;     // [n][4] xyxy
+  const int* pairs;     // [npairs][2], i < j
+  int n, th, tw, npairs;
+  double* offsets;  // [npairs]
+  int* status;      // [n], BSGP_COADD_* bits
+};
+struct CoaddSolveArgs {
+  int n, ncomp, bref;  // bref < 0: no background reference
+  const int *row_ptr, *nbr, *nbr_pair, *nbr_sign;  // adjacency lists (CSR) over the pairs
+  const int* component;                            // [n], 0 .. ncomp - 1
+  const double* offsets;                           // [npairs], NaN: the pair is dropped
+  double* c;       // [n] out
+  int* status;     // [n], bits are added
+  double* ws;      // [2 n]: residual, L p
+  double* info;    // [2] out (iterations, relative residual), or nullptr
+};
+hipError_t launch_pair_offsets(const CoaddOffsetArgs& a, hipStream_t s);
+hipError_t launch_solve_corrections(const CoaddSolveArgs& a, hipStream_t s);
+hipError_t launch_coadd_tiles_matched(const double* tiles, int n, int th, int tw, const int* boxes,
+                                      const double* corr, int H, int W, double* mean,
+                                      double* footprint, hipStream_t s);
 // ---- sky background (bsgp_background.hip) ----------------------
 constexpr int kBkgMaxBox = 4096;    // pixels of one box: its sorted copy is 32 KiB of LDS
 constexpr int kBkgMaxCells = 4096;  // cells of one image's mesh (k_bkg_mesh keeps two copies in LDS)

@@ -12,10 +12,22 @@ whole chain stays in HBM:
   mosaic, footprint = coadd_tiles(out, boxes)   # bsgp_coadd_tiles, mean in tile order
 
 ``sgp_subdivisions`` runs the chain.  The co-add is the same-WCS case of
-reproject_and_coadd with combine_function='mean'; its ``match_background``
-offset fit (utils.py:391) is not reproduced (parity of that step is unpinned:
-the reproject package is absent here).
+reproject_and_coadd with combine_function='mean'.  ``match_background=True``
+adds the reference's ``match_background`` (utils.py:392-397), also on the
+device: every tile is solved on its own, so neighbours
+disagree by a constant where they overlap and a plain mean leaves a step along
+every tile border.  ``tile_pairs`` lists the overlapping pairs (host, integer
+geometry), ``match_tile_backgrounds`` takes the median difference of every
+pair in its overlap (bit-equal to ``numpy.median``) and solves for the
+per-tile corrections: the minimum-norm least-squares solution of
+c_i - c_j = O_ij, the fixed point that reproject's shuffled gradient descent
+converges to whatever its shuffles, so the step is deterministic here.  The
+co-add then takes c_t off tile t.  What stays out: reprojection between grids,
+a ``combine_function`` other than the mean, weights, and reproject's NaN
+correction for a tile that overlaps no other (it gets 0 and a status bit).
 """
+import warnings
+
 import numpy as np
 
 import _bsgp as _B
@@ -84,10 +96,235 @@ def extract_tiles(image, boxes, subdiv_shape):
     return out
 
 
-def coadd_tiles(tiles, boxes, shape):
-    """Mean mosaic [H, W] and footprint [H, W] (tiles covering each pixel)."""
+class TileMatchWarning(UserWarning):
+    """The background matching dropped a pair, met a tile without a pair, or
+    its solver stopped at the iteration cap."""
+
+
+class TilePairs:
+    """B1, the geometry of the matching (host arrays, int32): ``pairs`` [P, 2]
+    (i < j, ordered by (i, j)), ``rects`` [P, 4] their xyxy intersections, the
+    adjacency lists ``row_ptr`` [n + 1], ``nbr``, ``nbr_pair``, ``nbr_sign``
+    [2 P] (row i: its neighbours in index order, the pair's index, +1 where i
+    is the pair's first tile, else -1), ``component`` [n] numbered by their
+    first tile, and ``ncomp``."""
+
+    def __init__(self, n, pairs, rects, row_ptr, nbr, nbr_pair, nbr_sign, component, ncomp):
+        self.n, self.pairs, self.rects = n, pairs, rects
+        self.row_ptr, self.nbr, self.nbr_pair, self.nbr_sign = row_ptr, nbr, nbr_pair, nbr_sign
+        self.component, self.ncomp = component, ncomp
+
+
+def tile_pairs(boxes):
+    """Every unordered pair of boxes (xyxy) that intersect in a non-empty
+    rectangle -- side and diagonal neighbours, and the inward-shifted edge
+    tiles of ``calculate_slice_bboxes`` -- with the adjacency lists and the
+    connected components the solver walks (:class:`TilePairs`).  Host only."""
+    b = np.asarray(boxes, dtype=np.int64).reshape(-1, 4)
+    n = len(b)
+    pi, pj, rc = [], [], []
+    for i in range(n - 1):
+        o = b[i + 1:]
+        r = np.stack([np.maximum(b[i, 0], o[:, 0]), np.maximum(b[i, 1], o[:, 1]),
+                      np.minimum(b[i, 2], o[:, 2]), np.minimum(b[i, 3], o[:, 3])], axis=1)
+        hit = np.nonzero((r[:, 2] > r[:, 0]) & (r[:, 3] > r[:, 1]))[0]
+        pi.append(np.full(len(hit), i))
+        pj.append(hit + i + 1)
+        rc.append(r[hit])
+    pi = np.concatenate(pi) if pi else np.zeros(0, np.int64)
+    pj = np.concatenate(pj) if pj else np.zeros(0, np.int64)
+    rects = (np.concatenate(rc) if rc else np.zeros((0, 4))).astype(np.int32).reshape(-1, 4)
+    P = len(pi)
+    rows, nb = np.concatenate([pi, pj]), np.concatenate([pj, pi])
+    order = np.lexsort((nb, rows))
+    row_ptr = np.concatenate([[0], np.cumsum(np.bincount(rows, minlength=n))]).astype(np.int32)
+    pair_idx = np.concatenate([np.arange(P), np.arange(P)])[order]
+    sign = np.concatenate([np.ones(P), -np.ones(P)])[order]
+    parent = list(range(n))  # union-find, the smaller root wins
+
+    def find(k):
+        while parent[k] != k:
+            parent[k] = parent[parent[k]]
+            k = parent[k]
+        return k
+
+    for i, j in zip(pi.tolist(), pj.tolist()):
+        ri, rj = find(i), find(j)
+        if ri != rj:
+            parent[max(ri, rj)] = min(ri, rj)
+    roots = np.asarray([find(k) for k in range(n)], dtype=np.int64)
+    _, comp = np.unique(roots, return_inverse=True)  # (roots are first tiles: numbered in order)
+    return TilePairs(n, np.stack([pi, pj], axis=1).astype(np.int32).reshape(-1, 2), rects, row_ptr,
+                     nb[order].astype(np.int32), pair_idx.astype(np.int32), sign.astype(np.int32),
+                     comp.astype(np.int32).reshape(-1), int(comp.max()) + 1 if n else 0)
+
+
+class TileMatch:
+    """The background matching of a set of tiles: ``pairs`` [P, 2] (host),
+    ``offsets`` [P] (B2; NaN for a dropped pair), ``corrections`` [n] (B3),
+    ``status`` [n] (``_bsgp.BSGP_COADD_*`` bits) and ``solve_info``
+    (iterations, relative residual of the conjugate gradients); numpy arrays,
+    or CUDA tensors with ``device_out``.  ``geometry`` is the :class:`TilePairs`."""
+
+    def __init__(self, geometry, offsets, corrections, status, solve_info, background_reference):
+        self.geometry, self.pairs = geometry, geometry.pairs
+        self.offsets, self.corrections, self.status = offsets, corrections, status
+        self.solve_info = solve_info
+        self.background_reference = background_reference
+
+    def __getitem__(self, key):
+        return getattr(self, key)
+
+    @property
+    def offset_matrix(self):
+        """[n, n] in reproject's layout: O[i, j] = -O[j, i] = the offset of
+        pair (i, j), NaN where two tiles do not overlap (and on the diagonal)."""
+        n, pr = self.geometry.n, self.pairs
+        if _B.torch is not None and _B.torch.is_tensor(self.offsets):
+            torch = _B.torch
+            m = torch.full((n, n), float("nan"), dtype=torch.float64, device=self.offsets.device)
+            if len(pr):
+                i = torch.from_numpy(pr[:, 0].astype(np.int64)).to(m.device)
+                j = torch.from_numpy(pr[:, 1].astype(np.int64)).to(m.device)
+                m[i, j] = self.offsets
+                m[j, i] = -self.offsets
+            return m
+        m = np.full((n, n), np.nan)
+        m[pr[:, 0], pr[:, 1]] = self.offsets
+        m[pr[:, 1], pr[:, 0]] = -np.asarray(self.offsets)
+        return m
+
+    def to_host(self, warn=True):
+        """The same match with numpy arrays (waits for the stream); warns on
+        the status bits."""
+        if _B.torch is not None and _B.torch.is_tensor(self.offsets):
+            h = _B.to_host({"o": self.offsets, "c": self.corrections, "s": self.status,
+                            "i": self.solve_info})
+            m = TileMatch(self.geometry, h["o"], h["c"], h["s"], h["i"], self.background_reference)
+        else:
+            m = self
+        if warn:
+            m.warn()
+        return m
+
+    def warn(self):
+        st = np.asarray(self.status)
+        if np.any(st & _B.BSGP_COADD_NONFINITE):
+            bad = int(np.sum(~np.isfinite(np.asarray(self.offsets))))
+            warnings.warn(f"{bad} pair(s) of tiles with a non-finite value in their overlap were "
+                          "left out of the background matching", TileMatchWarning)
+        iso = np.nonzero(st & _B.BSGP_COADD_ISOLATED)[0]
+        if iso.size:
+            warnings.warn(f"{iso.size} tile(s) overlap no other tile (first: {iso[:8].tolist()}): "
+                          "their background correction is 0", TileMatchWarning)
+        if np.any(st & _B.BSGP_COADD_NOT_CONVERGED):
+            warnings.warn("the background corrections did not converge within one iteration per "
+                          f"tile (relative residual {float(self.solve_info[1]):.3g})",
+                          TileMatchWarning)
+
+
+def _tiles_boxes(tiles, boxes):
+    torch = _B.torch
+    t = tiles if torch.is_tensor(tiles) else _B.to_dev(np.asarray(tiles, dtype=np.float64))
+    t = t.to(dtype=torch.float64).contiguous()
+    b = np.asarray(boxes, dtype=np.int32).reshape(-1, 4)
+    if len(b) != t.shape[0]:
+        raise ValueError("one box per tile")
+    return t, b
+
+
+_geometry = {}  # (boxes' bytes, device) -> (TilePairs, its device copy, the copy's sections)
+
+
+def _geometry_dev(b):
+    """B1 of boxes ``b`` and its one upload (boxes, pairs, adjacency lists,
+    components in one int32 tensor).  The last few layouts are kept: a field's
+    image, background and rms mosaics share their boxes (sgp.py:1089-1091), and
+    the pair search is host work during which the device would idle."""
+    torch = _B.torch
+    key = (b.tobytes(), torch.cuda.current_device())
+    hit = _geometry.get(key)
+    if hit is None:
+        g = tile_pairs(b)
+        parts = [b.reshape(-1), g.pairs.reshape(-1), g.row_ptr, g.nbr, g.nbr_pair, g.nbr_sign,
+                 g.component]
+        geo = torch.from_numpy(np.ascontiguousarray(np.concatenate(parts), dtype=np.int32))
+        hit = (g, geo.to("cuda"), [len(p) for p in parts])
+        if len(_geometry) >= 8:
+            _geometry.pop(next(iter(_geometry)))
+        _geometry[key] = hit
+    return hit
+
+
+def _match_dev(t, b, background_reference):
+    """B1 on the host, B2 and B3 on the device (asynchronous): a TileMatch of
+    CUDA tensors, and the device copy of the boxes."""
+    torch = _B.torch
+    n, th, tw = t.shape
+    if np.any(b[:, 2] - b[:, 0] > tw) or np.any(b[:, 3] - b[:, 1] > th) or \
+            np.any(b[:, 2] <= b[:, 0]) or np.any(b[:, 3] <= b[:, 1]):
+        raise ValueError("every box must be non-empty and no larger than a tile")
+    if background_reference is not None:
+        k = int(background_reference)
+        if k != background_reference or not 0 <= k < n:
+            raise ValueError(f"background_reference must be a tile index in 0..{n - 1} or None")
+    g, geo, sizes = _geometry_dev(b)
+    P = len(g.pairs)
+    bd, prd, row_ptr, nbr, nbr_pair, nbr_sign, comp = torch.split(geo, sizes)
+    f64 = dict(dtype=torch.float64, device="cuda")
+    offsets, corr, info = torch.empty(P, **f64), torch.empty(n, **f64), torch.empty(2, **f64)
+    status = torch.empty(n, dtype=torch.int32, device="cuda")
+    L, s = _B.lib(), _B.current_stream()
+    _B.check(L.bsgp_tile_offsets(_B._ptr(t), n, th, tw, _B._ptr(bd), _B._ptr(prd), P,
+                                 _B._ptr(offsets), _B._ptr(status), s))
+    _B.check(L.bsgp_tile_corrections(n, _B._ptr(row_ptr), _B._ptr(nbr), _B._ptr(nbr_pair),
+                                     _B._ptr(nbr_sign), _B._ptr(comp), g.ncomp, _B._ptr(offsets),
+                                     -1 if background_reference is None else int(background_reference),
+                                     _B._ptr(corr), _B._ptr(status), _B._ptr(info), s))
+    m = TileMatch(g, offsets, corr, status, info, background_reference)
+    m._keep = (t, geo)
+    return m, bd
+
+
+def match_tile_backgrounds(tiles, boxes, background_reference=None, device_out=False):
+    """The per-tile background corrections of reproject_and_coadd's
+    ``match_background=True`` (utils.py:392-397) for tiles [n, th, tw] at
+    ``boxes`` on one pixel grid: a :class:`TileMatch`.  ``offsets`` are
+    bit-equal to ``numpy.median`` of the two tiles' difference over each
+    overlap; ``corrections`` solve c_i - c_j = O_ij in the least-squares sense
+    with zero mean in every connected component of the overlap graph, or with
+    ``c[background_reference] == 0`` (any tile index: 0 counts, which
+    reproject's ``if background_reference:`` overlooks).  Subtract
+    ``corrections[t]`` from tile t.  A pair whose overlap holds a non-finite
+    difference is dropped, a tile without a pair keeps correction 0; both set
+    a status bit and warn (with ``device_out`` nothing waits for the device:
+    the bits are in ``status``, and ``to_host()`` warns)."""
+    _B.require_gpu()
+    t, b = _tiles_boxes(tiles, boxes)
+    m, _ = _match_dev(t, b, background_reference)
+    return m if device_out else m.to_host()
+
+
+def coadd_tiles(tiles, boxes, shape, match_background=False, background_reference=None):
+    """Mean mosaic [H, W] and footprint [H, W] (tiles covering each pixel).
+    ``match_background=True``: the tiles' background corrections
+    (:func:`match_tile_backgrounds`, all on the device) are taken off before
+    the mean, and ``mean._match`` keeps the :class:`TileMatch` (CUDA tensors)."""
     _B.require_gpu()
     torch = _B.torch
+    if match_background:
+        t, b = _tiles_boxes(tiles, boxes)
+        n, th, tw = t.shape
+        m, bd = _match_dev(t, b, background_reference)
+        H, W = shape
+        mean = torch.empty((H, W), dtype=torch.float64, device="cuda")
+        foot = torch.empty((H, W), dtype=torch.float64, device="cuda")
+        _B.check(_B.lib().bsgp_coadd_tiles_matched(_B._ptr(t), n, th, tw, _B._ptr(bd),
+                                                   _B._ptr(m.corrections), H, W, _B._ptr(mean),
+                                                   _B._ptr(foot), _B.current_stream()))
+        mean._keep = (t, bd)
+        mean._match = m
+        return mean, foot
     t = tiles if torch.is_tensor(tiles) else _B.to_dev(np.asarray(tiles, dtype=np.float64))
     t = t.to(dtype=torch.float64).contiguous()
     n, th, tw = t.shape
@@ -158,7 +395,8 @@ def _segment_flux(sgp_kwargs, tiles, box_size, repeat=1, localbkg_width=0, deble
 
 def sgp_subdivisions(image, psf, bkg, subdiv_shape=(256, 256), overlap=32, betaParams=None,
                      device_out=False, bkg_box_size=None, bkg_filter_size=(3, 3),
-                     flux_localbkg_width=0, flux_deblend=False, **sgp_kwargs):
+                     flux_localbkg_width=0, flux_deblend=False, match_background=False,
+                     background_reference=None, **sgp_kwargs):
     """Field -> overlapping subdivisions -> one batched beta-SGP solve -> mean
     mosaic.  ``bkg``: scalar, or a field-sized map (cut like the image, as the
     application cuts its background map).  ``psf``: one stamp for every tile,
@@ -173,6 +411,9 @@ def sgp_subdivisions(image, psf, bkg, subdiv_shape=(256, 256), overlap=32, betaP
     ``flux_localbkg_width=5, flux_deblend=True`` is the reference's constraint
     (its catalogue subtracts a local background, utils.py:244-246), the
     defaults 0 and ``False`` leave the sums as they were.
+    ``match_background=True`` (with ``background_reference``) co-adds as the
+    reference does, the tiles' backgrounds matched first (:func:`coadd_tiles`);
+    the solve outputs then carry ``"bkg_match"``, the :class:`TileMatch`.
     Returns (mosaic, footprint, solve outputs); numpy unless device_out."""
     import sgp
     torch = _B.torch
@@ -198,18 +439,26 @@ def sgp_subdivisions(image, psf, bkg, subdiv_shape=(256, 256), overlap=32, betaP
                   deblend=flux_deblend)
     out = sgp.sgp_betaDiv_batch(tiles, psf, bk, betaParams=betaParams, device_out=True,
                                 **sgp_kwargs)
-    mosaic, foot = coadd_tiles(out["x"], boxes, (H, W))
+    mosaic, foot = coadd_tiles(out["x"], boxes, (H, W), match_background=match_background,
+                               background_reference=background_reference)
+    match = mosaic._match if match_background else None
     if device_out:
+        if match_background:
+            out["bkg_match"] = match
         return mosaic, foot, out
     torch.cuda.current_stream().synchronize()
     _B.check_status(out["counters"])
-    return mosaic.cpu().numpy(), foot.cpu().numpy(), \
-        {k: (v.cpu().numpy() if v is not None else None) for k, v in out.items()}
+    res = {k: (v.cpu().numpy() if v is not None else None) for k, v in out.items()}
+    if match_background:
+        res["bkg_match"] = match.to_host()
+    return mosaic.cpu().numpy(), foot.cpu().numpy(), res
 
 
 def sgp_subdivisions_multistart(image, psf, bkg, betas=None, score=None, subdiv_shape=(256, 256),
                                 overlap=32, bkg_box_size=None, bkg_filter_size=(3, 3),
-                                flux_localbkg_width=0, flux_deblend=False, **sgp_kwargs):
+                                flux_localbkg_width=0, flux_deblend=False,
+                                match_background=False, background_reference=None,
+                                **sgp_kwargs):
     """The application's beta search for every subdivision of a field at once
     (application_sgp_subdivisions.py:69-107 per tile): the (tile x candidate)
     product -- n tiles x K initial betas (default: the application's five
@@ -227,7 +476,9 @@ def sgp_subdivisions_multistart(image, psf, bkg, betas=None, score=None, subdiv_
     discrepancy ranks the candidates.  ``flux="segments"``,
     ``flux_localbkg_width`` and ``flux_deblend`` as in :func:`sgp_subdivisions`.  ``psf``,
     ``bkg`` (``"estimate"`` with ``bkg_box_size`` included) and the keyword
-    arguments as in :func:`sgp_subdivisions`.
+    arguments as in :func:`sgp_subdivisions`; so are ``match_background`` and
+    ``background_reference``, and ``info["bkg_match"]`` then holds the
+    :class:`TileMatch` of the chosen candidates.
     Returns (mosaic, footprint, info): info holds the boxes, "betas",
     "scores" [n, K], "best" [n] (candidate index per tile), "best_beta" [n],
     and the solve outputs of the chosen candidates ("x", "iters", "discr",
@@ -281,9 +532,12 @@ def sgp_subdivisions_multistart(image, psf, bkg, betas=None, score=None, subdiv_
     best = np.asarray(best)
     pick = np.arange(n) * K + best
     xs = out["x"][pick]
-    mosaic, foot = coadd_tiles(xs, boxes, (H, W))
+    mosaic, foot = coadd_tiles(xs, boxes, (H, W), match_background=match_background,
+                               background_reference=background_reference)
     info = {"boxes": boxes, "betas": betas, "scores": scores, "best": best,
             "best_beta": np.asarray(betas)[best], "x": xs, "iters": out["iters"][pick],
             "discr": out["discr"][pick], "beta_final": out["beta_final"][pick]}
     torch.cuda.current_stream().synchronize()
+    if match_background:
+        info["bkg_match"] = mosaic._match.to_host()
     return mosaic.cpu().numpy(), foot.cpu().numpy(), info

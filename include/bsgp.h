@@ -242,9 +242,60 @@ int bsgp_extract_tiles(const double* img, int32_t H, int32_t W, const int32_t* b
  * (may be NULL) = number of tiles covering each pixel; uncovered pixels are 0.
  * Tiles are summed in index order (deterministic).  The same-WCS case of
  * reproject_and_coadd (utils.py:389-395) with combine_function='mean' and no
- * background matching.  n <= 8192.  Asynchronous. */
+ * background matching (bsgp_coadd_tiles_matched below has it).  n <= 8192.
+ * Asynchronous. */
 int bsgp_coadd_tiles(const double* tiles, int32_t n, int32_t th, int32_t tw, const int32_t* boxes,
                      int32_t H, int32_t W, double* mean, double* footprint, void* stream);
+
+/* ---- background-matched co-add --------------------
+ * reproject_and_coadd(..., match_background=True) for tiles on one pixel grid
+ * (restoration/utils.py:392-397), in three asynchronous steps whose arguments
+ * all live on the device.  The pairs of overlapping tiles, their adjacency
+ * lists and the connected components (B1) are integer geometry of the boxes
+ * and come from the caller (beta-sgp_amd/subdivisions.py tile_pairs).
+ * n <= 8192 as for bsgp_coadd_tiles; th * tw < 2^31. */
+#define BSGP_COADD_NONFINITE 1      /* a pair of this tile held a non-finite difference: dropped */
+#define BSGP_COADD_ISOLATED 2       /* no pair (left): correction 0                              */
+#define BSGP_COADD_NOT_CONVERGED 4  /* the solver stopped at its iteration cap                   */
+
+/* B2 (utils.py:392-397): offsets[p] = numpy.median(tile_i - tile_j) over the
+ * intersection of boxes i and j for pairs[p] = {i, j}, i < j (int32
+ * [npairs][2]); bit-equal to numpy.median (the middle value of an odd count,
+ * (lo + hi) / 2 of the two middle values of an even one).  A pair whose overlap
+ * holds a non-finite difference gets NaN, which drops it from the graph, and
+ * BSGP_COADD_NONFINITE in status of both tiles; so does a pair that does not
+ * intersect, without the bit.  status (int32 [n]) is zeroed first.  npairs may
+ * be 0.  Asynchronous. */
+int bsgp_tile_offsets(const double* tiles, int32_t n, int32_t th, int32_t tw, const int32_t* boxes,
+                      const int32_t* pairs, int32_t npairs, double* offsets, int32_t* status,
+                      void* stream);
+
+/* B3 (utils.py:392-397): corrections = the minimum-norm least-squares solution
+ * of c_i - c_j = O_ij over the pairs with a finite offset, the fixed point of
+ * reproject's solve_corrections_sgd: conjugate gradients on the graph Laplacian
+ * from c = 0 in one workgroup, float64, fixed-order sums (deterministic), down
+ * to a relative residual of 1e-13 or n iterations (BSGP_COADD_NOT_CONVERGED in
+ * every status word); zero mean within every connected component; a tile
+ * without a pair gets 0 and BSGP_COADD_ISOLATED.  Row i's neighbours are
+ * nbr[row_ptr[i] .. row_ptr[i + 1]), nbr_pair the index of that pair in
+ * offsets, nbr_sign +1 where i is the pair's first tile (O_ij = offsets[pair])
+ * and -1 where it is the second; component [n] in 0 .. ncomp - 1.
+ * background_reference >= 0: c -= c[background_reference] afterwards; < 0: none.
+ * Bits are added to status (the one bsgp_tile_offsets wrote, or zeros).
+ * solve_info (may be NULL): {iterations, relative residual reached}.
+ * Asynchronous. */
+int bsgp_tile_corrections(int32_t n, const int32_t* row_ptr, const int32_t* nbr,
+                          const int32_t* nbr_pair, const int32_t* nbr_sign,
+                          const int32_t* component, int32_t ncomp, const double* offsets,
+                          int32_t background_reference, double* corrections, int32_t* status,
+                          double* solve_info, void* stream);
+
+/* B4 (utils.py:392-397): bsgp_coadd_tiles with corrections[t] taken off every
+ * value of tile t before it is added: mean = sum_t (tile_t - c_t) / count in
+ * tile order; the footprint is bsgp_coadd_tiles'.  n <= 8192.  Asynchronous. */
+int bsgp_coadd_tiles_matched(const double* tiles, int32_t n, int32_t th, int32_t tw,
+                             const int32_t* boxes, const double* corrections, int32_t H, int32_t W,
+                             double* mean, double* footprint, void* stream);
 
 /* FITS primary-array samples (big-endian, BITPIX 8/16/32/64/-32/-64) to f64:
  * out[i] = BZERO + BSCALE * sample[i] (FITS standard 4.0 §5.3; IEEE samples
