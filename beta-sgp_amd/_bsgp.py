@@ -51,6 +51,11 @@ BSGP_STAMP_NO_CANDIDATE, BSGP_STAMP_RESTORED_NO_SOURCE = 64, 128
 BSGP_STAMP_ROW_COLS = 11  # columns of a bsgp_stamp_select result row
 # status bits of the background-matched co-add (include/bsgp.h)
 BSGP_COADD_NONFINITE, BSGP_COADD_ISOLATED, BSGP_COADD_NOT_CONVERGED = 1, 2, 4
+# bsgp_convolve2d_ex (include/bsgp.h): kernel size per axis, flags, status bits
+BSGP_CONV_MAX_KERNEL = 63
+BSGP_CONV_F_INTERPOLATE, BSGP_CONV_F_FILL = 0, 1
+BSGP_CONV_F_NORMALIZE, BSGP_CONV_F_PRESERVE_NAN = 2, 4
+BSGP_CONV_HAD_NAN, BSGP_CONV_NAN_LEFT = 1, 2
 
 
 class BsgpError(RuntimeError):
@@ -185,6 +190,8 @@ def lib():
             L.bsgp_background2d.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, i32, dbl, i32,
                                             dbl, i32, vp, vp, vp, vp, vp, vp, vp, vp]
             L.bsgp_convolve2d.argtypes = [vp, i32, i32, i32, i32, vp, i32, i32, vp, vp]
+            L.bsgp_convolve2d_ex.argtypes = [vp, i32, i32, i32, i32, vp, i32, i32, i32, vp, vp,
+                                             i32, dbl, vp, vp, vp]
             L.bsgp_detect_sources.argtypes = [vp, i32, i32, i32, i32, vp, dbl, i32, i32, vp, vp,
                                               vp, vp]
             L.bsgp_segment_catalog.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]
@@ -218,7 +225,7 @@ def lib():
                          "bsgp_deblend_sources_large", "bsgp_segment_local_background",
                          "bsgp_match_catalogs", "bsgp_extract_stamps", "bsgp_stamp_select",
                          "bsgp_tile_offsets", "bsgp_tile_corrections",
-                         "bsgp_coadd_tiles_matched"]:
+                         "bsgp_coadd_tiles_matched", "bsgp_convolve2d_ex"]:
                 getattr(L, name).restype = ctypes.c_int
             if L.bsgp_abi_version() != ABI_VERSION:
                 raise BsgpError(-3, f"{LIB_PATH} has ABI {L.bsgp_abi_version()}, this binding "
@@ -238,7 +245,7 @@ EXPORTED = ["bsgp_plan_create", "bsgp_plan_create_checked", "bsgp_plan_destroy",
             "bsgp_fit_gauss1d", "bsgp_wasserstein1", "bsgp_deblend_sources",
             "bsgp_deblend_sources_large", "bsgp_segment_local_background", "bsgp_match_catalogs",
             "bsgp_extract_stamps", "bsgp_stamp_select", "bsgp_tile_offsets",
-            "bsgp_tile_corrections", "bsgp_coadd_tiles_matched"]
+            "bsgp_tile_corrections", "bsgp_coadd_tiles_matched", "bsgp_convolve2d_ex"]
 
 
 def check(rc):

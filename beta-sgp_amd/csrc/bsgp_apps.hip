@@ -246,6 +246,41 @@ int bsgp_convolve2d(const void* data, int32_t dtype, int32_t B, int32_t H, int32
   return BSGP_OK;
 }
 
+int bsgp_convolve2d_ex(const void* data, int32_t dtype, int32_t B, int32_t H, int32_t W,
+                       const double* kernel, int32_t kh, int32_t kw, int32_t kernel_stride,
+                       const double* kernel_sum, const uint8_t* mask, int32_t flags,
+                       double fill_value, double* out, int32_t* status_out, void* stream) {
+  if (!data) return fail(BSGP_ERR_ARG, "data is NULL");
+  if (!kernel) return fail(BSGP_ERR_ARG, "kernel is NULL");
+  if (!kernel_sum) return fail(BSGP_ERR_ARG, "kernel_sum is NULL");
+  if (!out) return fail(BSGP_ERR_ARG, "out is NULL");
+  if (!status_out) return fail(BSGP_ERR_ARG, "status_out is NULL");
+  if (dtype != BSGP_DTYPE_F32 && dtype != BSGP_DTYPE_F64)
+    return fail(BSGP_ERR_ARG, "dtype must be BSGP_DTYPE_F32 or BSGP_DTYPE_F64");
+  if (kh < 1 || kw < 1) return fail(BSGP_ERR_ARG, "kernel size (kh, kw) must be >= 1");
+  if (flags & ~(BSGP_CONV_F_FILL | BSGP_CONV_F_NORMALIZE | BSGP_CONV_F_PRESERVE_NAN))
+    return fail(BSGP_ERR_ARG, "flags holds an unknown bit");
+  if (!std::isfinite(fill_value)) return fail(BSGP_ERR_ARG, "fill_value must be finite");
+  if (int rc = seg_shape(B, H, W)) return rc;
+  if (kh % 2 == 0 || kw % 2 == 0 || kh > kConvMaxKernel || kw > kConvMaxKernel) {
+    char msg[128];
+    snprintf(msg, sizeof msg, "kernel of %d x %d: kernels are odd and at most %d x %d", kh, kw,
+             kConvMaxKernel, kConvMaxKernel);
+    return fail(BSGP_ERR_UNSUPPORTED, msg);
+  }
+  if (kernel_stride != 0 && kernel_stride != kh * kw)
+    return fail(BSGP_ERR_ARG, "kernel_stride must be 0 (one kernel) or kh * kw (one per image)");
+  if (conv_tiles(H, W, kh, kw) > 0xffffffLL)  // workgroups of 256 threads: a grid below 2^32
+    return fail(BSGP_ERR_UNSUPPORTED, "an image is covered by at most 2^24 - 1 tiles of 64 columns");
+  ConvArgs a{};
+  a.data = data, a.kernel = kernel, a.kernel_sum = kernel_sum, a.mask = mask;
+  a.fill_value = fill_value, a.out = out, a.status = status_out;
+  a.B = B, a.H = H, a.W = W, a.kh = kh, a.kw = kw, a.kernel_stride = kernel_stride;
+  a.flags = flags;
+  HIP_TRY(launch_convolve(a, dtype == BSGP_DTYPE_F32, (hipStream_t)stream));
+  return BSGP_OK;
+}
+
 int bsgp_detect_sources(const void* data, int32_t dtype, int32_t B, int32_t H, int32_t W,
                         const double* threshold_map, double threshold, int32_t npixels,
                         int32_t connectivity, const uint8_t* mask, int32_t* labels_out,

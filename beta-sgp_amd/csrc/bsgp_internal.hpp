@@ -236,6 +236,22 @@ struct SegCatArgs {
 hipError_t launch_seg_convolve(const SegConvArgs& a, int f32, hipStream_t s);
 hipError_t launch_seg_detect(const SegArgs& a, int f32, hipStream_t s);
 hipError_t launch_seg_catalog(const SegCatArgs& a, hipStream_t s);
+// ---- PSF-sized convolution (bsgp_convolve.hip) ----------------
+constexpr int kConvMaxKernel = BSGP_CONV_MAX_KERNEL;  // per axis (odd)
+struct ConvArgs {
+  const void* data;           // [B][H][W] float32 or float64
+  const double* kernel;       // [kh][kw], or [B][kh][kw] at kernel_stride = kh * kw
+  const double* kernel_sum;   // [1], or [B] with per-image kernels
+  const unsigned char* mask;  // [B][H][W] bytes, nonzero = masked, or nullptr
+  double fill_value;
+  double* out;  // [B][H][W]
+  int* status;  // [B]: BSGP_CONV_HAD_NAN | BSGP_CONV_NAN_LEFT
+  int B, H, W, kh, kw, kernel_stride, flags;
+  int ntx;  // tiles per tile row (the launch fills it in)
+};
+int conv_rows_per_thread(int H, int kh, int kw);
+int64_t conv_tiles(int H, int W, int kh, int kw);  // workgroups per image
+hipError_t launch_convolve(const ConvArgs& a, int f32, hipStream_t s);
 // ---- local background (bsgp_localbkg.hip) ------------
 constexpr int kLocalBkgMax = BSGP_LOCALBKG_MAX;  // values of one annulus: 64 KiB of LDS
 struct LocalBkgArgs {

@@ -469,6 +469,44 @@ int bsgp_solve_resume(bsgp_plan plan, int32_t B, const bsgp_params* params,
  * (dtype), widened first; out: float64 [B][H][W]; H <= 65535. */
 int bsgp_convolve2d(const void* data, int32_t dtype, int32_t B, int32_t H, int32_t W,
                     const double* kernel, int32_t kh, int32_t kw, double* out, void* stream);
+/* bsgp_convolve2d_ex: astropy.convolution.convolve(array, kernel,
+ * boundary='fill', fill_value, nan_treatment, normalize_kernel, mask,
+ * preserve_nan) for kernels the size of a PSF (utils.py:46-56 degrade,
+ * :249-272 scale_psf).  The sum is bsgp_convolve2d's: per output
+ * pixel the taps run in row-major order of the window, tap (i, j) times
+ * K[kh-1-i][kw-1-j], every product and sum rounded; a tap outside the image
+ * contributes fill_value * k.
+ *   kernel: device float64 [kh][kw] (kernel_stride 0, one for all images) or
+ *   [B][kh][kw] (kernel_stride kh * kw, image b with kernel b); kh and kw odd
+ *   and at most BSGP_CONV_MAX_KERNEL (else BSGP_ERR_UNSUPPORTED).
+ *   kernel_sum: device float64 [1] or [B]: numpy's sum of each kernel, which
+ *   the caller computes (it is not restated on the device).
+ *   mask: uint8 [B][H][W], nonzero = masked (treated as NaN), or NULL.
+ *   flags: BSGP_CONV_F_FILL replaces NaN and masked pixels by fill_value first
+ *   (nan_treatment='fill'); without it (BSGP_CONV_F_INTERPOLATE) an image that
+ *   holds a NaN or masked pixel takes, at every pixel, top / bot over the taps
+ *   whose value is not NaN (bot: the sum of their kernel entries, same order),
+ *   or data[y][x] where bot == 0, times kernel_sum without
+ *   BSGP_CONV_F_NORMALIZE.  Every other image: top / kernel_sum with
+ *   BSGP_CONV_F_NORMALIZE, else top.  BSGP_CONV_F_PRESERVE_NAN: NaN wherever
+ *   the input was NaN or masked.  Infinities are values.
+ *   fill_value must be finite.  data: float32 or float64 (dtype), widened
+ *   first; out: float64 [B][H][W].
+ *   status_out: device int32 [B]: BSGP_CONV_HAD_NAN the image held a NaN or a
+ *   masked pixel, BSGP_CONV_NAN_LEFT some output is NaN that
+ *   BSGP_CONV_F_PRESERVE_NAN did not put there.
+ * Asynchronous; no host synchronisation. */
+#define BSGP_CONV_MAX_KERNEL 63
+#define BSGP_CONV_F_INTERPOLATE 0
+#define BSGP_CONV_F_FILL 1
+#define BSGP_CONV_F_NORMALIZE 2
+#define BSGP_CONV_F_PRESERVE_NAN 4
+#define BSGP_CONV_HAD_NAN 1
+#define BSGP_CONV_NAN_LEFT 2
+int bsgp_convolve2d_ex(const void* data, int32_t dtype, int32_t B, int32_t H, int32_t W,
+                       const double* kernel, int32_t kh, int32_t kw, int32_t kernel_stride,
+                       const double* kernel_sum, const uint8_t* mask, int32_t flags,
+                       double fill_value, double* out, int32_t* status_out, void* stream);
 /* photutils' detect_sources (utils.py:243): a pixel is detected where data >
  * threshold (threshold_map [B][H][W] float64, or the scalar when it is NULL),
  * both finite and mask (bytes, nonzero = masked, or NULL) clear.  Components of
