@@ -143,6 +143,64 @@ STATE_SECTIONS = ("discr", "crit", "times", "flags", "x", "g", "x_tf", "pw", "gn
 _lib = None
 _lib_lock = threading.Lock()
 
+_i32, _i64, _dbl = ctypes.c_int32, ctypes.c_int64, ctypes.c_double
+# Every entry point of include/bsgp.h that returns a status (int): its argument
+# types, in the header's order.  lib() sets argtypes and restype from this one
+# table and EXPORTED is its keys (plus the two below that return something
+# else); tests/test_abi.py holds each entry's length against the declaration.
+_ENTRY_POINTS = {
+    "bsgp_plan_create": [_i32, _i32, _P, _i32, _i32, _i32, _i32, _i32, ctypes.POINTER(_P)],
+    "bsgp_plan_create_checked": [_i32, _i32, _P, _i32, _i32, _i32, _i32, _i32, _i32,
+                                 ctypes.POINTER(_P)],
+    "bsgp_plan_destroy": [_P],
+    "bsgp_plan_info": [_P, _P, _P, _P, _P],
+    "bsgp_solve_device": [_P, _i32, _P, _P, _P, _P],
+    "bsgp_solve_host": [_P, _i32, _P, _P, _P],
+    "bsgp_solve_profiled": [_P, _i32, _P, _P, _P, _P, _P, _P],
+    "bsgp_apply_operator": [_P, _i32, _i32, _P, _P, _P],
+    "bsgp_project_df": [_i64, _dbl, _P, _P, _dbl, _i32, _dbl, _dbl, _dbl, _dbl, _i32, _i32, _i32,
+                        _P, _P, _P],
+    "bsgp_beta_div": [_i64, _P, _P, _dbl, _P, _P],
+    "bsgp_beta_div_deriv": [_i64, _P, _P, _dbl, _P, _P],
+    "bsgp_beta_div_grad_parts": [_i64, _P, _P, _dbl, _P, _P, _P],
+    "bsgp_device_synchronize": [],
+    "bsgp_extract_tiles": [_P, _i32, _i32, _P, _i32, _i32, _i32, _P, _P],
+    "bsgp_coadd_tiles": [_P, _i32, _i32, _i32, _P, _i32, _i32, _P, _P, _P],
+    "bsgp_tile_offsets": [_P, _i32, _i32, _i32, _P, _P, _i32, _P, _P, _P],
+    "bsgp_tile_corrections": [_i32, _P, _P, _P, _P, _P, _i32, _P, _i32, _P, _P, _P, _P],
+    "bsgp_coadd_tiles_matched": [_P, _i32, _i32, _i32, _P, _P, _i32, _i32, _P, _P, _P],
+    "bsgp_fits_to_f64": [_P, _i64, _i32, _dbl, _dbl, _P, _P],
+    "bsgp_psf_stamps": [ctypes.POINTER(PsfModel), _P, _i32, _i32, _i32, _P, _P],
+    "bsgp_plan_set_psfs": [_P, _P, _i32, _P],
+    "bsgp_plan_set_static_geo": [_P, _i32],
+    "bsgp_plan_static_geo": [_P, _P],
+    "bsgp_state_layout": [_i32, _i32, _i32, _i32, _i32, _P],
+    "bsgp_state_bytes": [_P, _i32, _i32, ctypes.POINTER(_i64)],
+    "bsgp_state_save": [_P, _i32, _P, _i64, _P],
+    "bsgp_solve_resume": [_P, _i32, _P, _P, _i32, _i64, _P, _P, _P],
+    "bsgp_background2d": [_P, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _dbl, _i32, _dbl,
+                          _i32, _P, _P, _P, _P, _P, _P, _P, _P],
+    "bsgp_convolve2d": [_P, _i32, _i32, _i32, _i32, _P, _i32, _i32, _P, _P],
+    "bsgp_convolve2d_ex": [_P, _i32, _i32, _i32, _i32, _P, _i32, _i32, _i32, _P, _P, _i32, _dbl,
+                           _P, _P, _P],
+    "bsgp_detect_sources": [_P, _i32, _i32, _i32, _i32, _P, _dbl, _i32, _i32, _P, _P, _P, _P],
+    "bsgp_segment_catalog": [_P, _P, _P, _i32, _i32, _i32, _i32, _P, _P, _P, _P, _P],
+    "bsgp_deblend_sources": [_P, _P, _i32, _i32, _i32, _i32, _P, _P, _P, _i32, _i32, _dbl, _i32,
+                             _i32, _P, _P, _P, _P],
+    "bsgp_deblend_sources_large": [_P, _P, _i32, _i32, _i32, _i32, _P, _P, _P, _i32, _i32, _dbl,
+                                   _i32, _i32, _i32, _P, _P, _P, _P],
+    "bsgp_segment_local_background": [_P, _i32, _P, _i32, _i32, _i32, _i32, _P, _P, _P, _dbl,
+                                      _dbl, _i32, _i32, _i32, _P, _P, _P, _P],
+    "bsgp_match_catalogs": [_P, _P, _i32, _P, _i32, _i32, _P, _P, _P, _i32, _P, _i32, _i32, _P,
+                            _i32, _dbl, _i32, _P, _P, _P, _P, _P, _P],
+    "bsgp_radial_profile": [_P, _i32, _i32, _i32, _i32, _P, _i32, _P, _P, _P],
+    "bsgp_fit_gauss1d": [_P, _P, _i32, _i32, _P, _P, _P, _P, _P, _P],
+    "bsgp_wasserstein1": [_P, _P, _P, _P, _i32, _i32, _P, _P],
+    "bsgp_extract_stamps": [_P, _i32, _i32, _i32, _P, _i32, _i32, _i32, _P, _P, _P, _P],
+    "bsgp_stamp_select": [_P, _P, _i32, _P, _i32, _P, _i32, _i32, _P, _P, _P, _P, _P, _P],
+}
+EXPORTED = list(_ENTRY_POINTS) + ["bsgp_last_error", "bsgp_abi_version"]
+
 
 def lib():
     """Load libbsgp.so once; raise loudly if it is absent."""
@@ -154,98 +212,16 @@ def lib():
             if not os.path.exists(LIB_PATH):
                 raise BsgpError(-3, f"{LIB_PATH} not built — run __graft_entry__.build()")
             L = ctypes.CDLL(LIB_PATH)
-            i32, i64, dbl, vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_double, ctypes.c_void_p
-            L.bsgp_last_error.restype = ctypes.c_char_p
-            L.bsgp_abi_version.restype = i32
-            L.bsgp_plan_create.argtypes = [i32, i32, vp, i32, i32, i32, i32, i32,
-                                           ctypes.POINTER(vp)]
-            L.bsgp_plan_create_checked.argtypes = [i32, i32, vp, i32, i32, i32, i32, i32, i32,
-                                                   ctypes.POINTER(vp)]
-            L.bsgp_plan_destroy.argtypes = [vp]
-            L.bsgp_plan_info.argtypes = [vp, vp, vp, vp, vp]
-            L.bsgp_solve_device.argtypes = [vp, i32, vp, vp, vp, vp]
-            L.bsgp_solve_host.argtypes = [vp, i32, vp, vp, vp]
-            L.bsgp_solve_profiled.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
-            L.bsgp_apply_operator.argtypes = [vp, i32, i32, vp, vp, vp]
-            L.bsgp_project_df.argtypes = [i64, dbl, vp, vp, dbl, i32, dbl, dbl, dbl, dbl, i32,
-                                          i32, i32, vp, vp, vp]
-            L.bsgp_beta_div.argtypes = [i64, vp, vp, dbl, vp, vp]
-            L.bsgp_beta_div_deriv.argtypes = [i64, vp, vp, dbl, vp, vp]
-            L.bsgp_beta_div_grad_parts.argtypes = [i64, vp, vp, dbl, vp, vp, vp]
-            L.bsgp_extract_tiles.argtypes = [vp, i32, i32, vp, i32, i32, i32, vp, vp]
-            L.bsgp_coadd_tiles.argtypes = [vp, i32, i32, i32, vp, i32, i32, vp, vp, vp]
-            L.bsgp_tile_offsets.argtypes = [vp, i32, i32, i32, vp, vp, i32, vp, vp, vp]
-            L.bsgp_tile_corrections.argtypes = [i32, vp, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp,
-                                                vp]
-            L.bsgp_coadd_tiles_matched.argtypes = [vp, i32, i32, i32, vp, vp, i32, i32, vp, vp, vp]
-            L.bsgp_fits_to_f64.argtypes = [vp, i64, i32, dbl, dbl, vp, vp]
-            L.bsgp_psf_stamps.argtypes = [ctypes.POINTER(PsfModel), vp, i32, i32, i32, vp, vp]
-            L.bsgp_plan_set_psfs.argtypes = [vp, vp, i32, vp]
-            L.bsgp_plan_set_static_geo.argtypes = [vp, i32]
-            L.bsgp_plan_static_geo.argtypes = [vp, vp]
-            L.bsgp_state_layout.argtypes = [i32, i32, i32, i32, i32, vp]
-            L.bsgp_state_bytes.argtypes = [vp, i32, i32, ctypes.POINTER(i64)]
-            L.bsgp_state_save.argtypes = [vp, i32, vp, i64, vp]
-            L.bsgp_solve_resume.argtypes = [vp, i32, vp, vp, i32, i64, vp, vp, vp]
-            L.bsgp_background2d.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, i32, dbl, i32,
-                                            dbl, i32, vp, vp, vp, vp, vp, vp, vp, vp]
-            L.bsgp_convolve2d.argtypes = [vp, i32, i32, i32, i32, vp, i32, i32, vp, vp]
-            L.bsgp_convolve2d_ex.argtypes = [vp, i32, i32, i32, i32, vp, i32, i32, i32, vp, vp,
-                                             i32, dbl, vp, vp, vp]
-            L.bsgp_detect_sources.argtypes = [vp, i32, i32, i32, i32, vp, dbl, i32, i32, vp, vp,
-                                              vp, vp]
-            L.bsgp_segment_catalog.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]
-            L.bsgp_deblend_sources.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp, i32, i32, dbl,
-                                               i32, i32, vp, vp, vp, vp]
-            L.bsgp_deblend_sources_large.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp, i32,
-                                                     i32, dbl, i32, i32, i32, vp, vp, vp, vp]
-            L.bsgp_segment_local_background.argtypes = [vp, i32, vp, i32, i32, i32, i32, vp, vp,
-                                                        vp, dbl, dbl, i32, i32, i32, vp, vp, vp,
-                                                        vp]
-            L.bsgp_match_catalogs.argtypes = [vp, vp, i32, vp, i32, i32, vp, vp, vp, i32, vp, i32,
-                                              i32, vp, i32, dbl, i32, vp, vp, vp, vp, vp, vp]
-            L.bsgp_radial_profile.argtypes = [vp, i32, i32, i32, i32, vp, i32, vp, vp, vp]
-            L.bsgp_fit_gauss1d.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]
-            L.bsgp_wasserstein1.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp]
-            L.bsgp_extract_stamps.argtypes = [vp, i32, i32, i32, vp, i32, i32, i32, vp, vp, vp, vp]
-            L.bsgp_stamp_select.argtypes = [vp, vp, i32, vp, i32, vp, i32, i32, vp, vp, vp, vp,
-                                            vp, vp]
-            for name in ["bsgp_plan_create", "bsgp_plan_create_checked", "bsgp_plan_destroy", "bsgp_plan_info",
-                         "bsgp_solve_device", "bsgp_solve_host", "bsgp_solve_profiled",
-                         "bsgp_apply_operator",
-                         "bsgp_project_df", "bsgp_beta_div", "bsgp_beta_div_deriv",
-                         "bsgp_beta_div_grad_parts", "bsgp_device_synchronize",
-                         "bsgp_extract_tiles", "bsgp_coadd_tiles", "bsgp_fits_to_f64",
-                         "bsgp_psf_stamps", "bsgp_plan_set_psfs", "bsgp_state_layout",
-                         "bsgp_state_bytes", "bsgp_state_save", "bsgp_solve_resume",
-                         "bsgp_background2d", "bsgp_convolve2d", "bsgp_detect_sources",
-                         "bsgp_segment_catalog", "bsgp_plan_set_static_geo",
-                         "bsgp_plan_static_geo", "bsgp_radial_profile", "bsgp_fit_gauss1d",
-                         "bsgp_wasserstein1", "bsgp_deblend_sources",
-                         "bsgp_deblend_sources_large", "bsgp_segment_local_background",
-                         "bsgp_match_catalogs", "bsgp_extract_stamps", "bsgp_stamp_select",
-                         "bsgp_tile_offsets", "bsgp_tile_corrections",
-                         "bsgp_coadd_tiles_matched", "bsgp_convolve2d_ex"]:
-                getattr(L, name).restype = ctypes.c_int
+            L.bsgp_last_error.argtypes, L.bsgp_last_error.restype = [], ctypes.c_char_p
+            L.bsgp_abi_version.argtypes, L.bsgp_abi_version.restype = [], _i32
+            for name, argtypes in _ENTRY_POINTS.items():
+                fn = getattr(L, name)
+                fn.argtypes, fn.restype = argtypes, ctypes.c_int
             if L.bsgp_abi_version() != ABI_VERSION:
                 raise BsgpError(-3, f"{LIB_PATH} has ABI {L.bsgp_abi_version()}, this binding "
                                     f"needs {ABI_VERSION}: rebuild with __graft_entry__.build()")
             _lib = L
     return _lib
-
-
-EXPORTED = ["bsgp_plan_create", "bsgp_plan_create_checked", "bsgp_plan_destroy", "bsgp_plan_info", "bsgp_solve_device",
-            "bsgp_solve_host", "bsgp_solve_profiled", "bsgp_apply_operator", "bsgp_project_df", "bsgp_beta_div",
-            "bsgp_beta_div_deriv", "bsgp_beta_div_grad_parts", "bsgp_device_synchronize",
-            "bsgp_last_error", "bsgp_abi_version", "bsgp_extract_tiles", "bsgp_coadd_tiles",
-            "bsgp_fits_to_f64", "bsgp_psf_stamps", "bsgp_plan_set_psfs", "bsgp_state_layout",
-            "bsgp_state_bytes", "bsgp_state_save", "bsgp_solve_resume", "bsgp_background2d",
-            "bsgp_convolve2d", "bsgp_detect_sources", "bsgp_segment_catalog",
-            "bsgp_plan_set_static_geo", "bsgp_plan_static_geo", "bsgp_radial_profile",
-            "bsgp_fit_gauss1d", "bsgp_wasserstein1", "bsgp_deblend_sources",
-            "bsgp_deblend_sources_large", "bsgp_segment_local_background", "bsgp_match_catalogs",
-            "bsgp_extract_stamps", "bsgp_stamp_select", "bsgp_tile_offsets",
-            "bsgp_tile_corrections", "bsgp_coadd_tiles_matched", "bsgp_convolve2d_ex"]
 
 
 def check(rc):

@@ -16,6 +16,15 @@
 
 using namespace bsgp;
 
+namespace {
+// the element type of an image argument: float32 or float64
+int check_dtype(int32_t dtype) {
+  if (dtype != BSGP_DTYPE_F32 && dtype != BSGP_DTYPE_F64)
+    return fail(BSGP_ERR_ARG, "dtype must be BSGP_DTYPE_F32 or BSGP_DTYPE_F64");
+  return BSGP_OK;
+}
+}  // namespace
+
 extern "C" {
 
 int bsgp_project_df(int64_t n, double b, const double* c, const double* dia, double scaling,
@@ -85,15 +94,10 @@ int bsgp_tile_corrections(int32_t n, const int32_t* row_ptr, const int32_t* nbr,
   a.c = corrections, a.status = status, a.info = solve_info;
   hipStream_t s = (hipStream_t)stream;
   // stream-ordered workspace: the call stays asynchronous
-  void* w = nullptr;
-  HIP_TRY(hipMallocAsync(&w, 2 * (size_t)n * sizeof(double), s));
-  a.ws = static_cast<double*>(w);
-  const hipError_t e = launch_solve_corrections(a, s);
-  const hipError_t ef = hipFreeAsync(w, s);
-  if (e != hipSuccess)
-    return fail(BSGP_ERR_HIP, std::string("corrections launch: ") + hipGetErrorString(e));
-  HIP_TRY(ef);
-  return BSGP_OK;
+  StreamScratch w(s);
+  if (int rc = w.alloc(2 * (size_t)n * sizeof(double))) return rc;
+  a.ws = static_cast<double*>(w.p);
+  return w.finish(launch_solve_corrections(a, s), "corrections");
 }
 
 int bsgp_coadd_tiles_matched(const double* tiles, int32_t n, int32_t th, int32_t tw,
@@ -156,8 +160,7 @@ int bsgp_background2d(const void* data, int32_t dtype, int32_t B, int32_t H, int
                       double* rms_out, double* mesh_out, double* rms_mesh_out, double* medians_out,
                       int32_t* status_out, void* stream) {
   if (!data) return fail(BSGP_ERR_ARG, "data is NULL");
-  if (dtype != BSGP_DTYPE_F32 && dtype != BSGP_DTYPE_F64)
-    return fail(BSGP_ERR_ARG, "dtype must be BSGP_DTYPE_F32 or BSGP_DTYPE_F64");
+  if (int rc = check_dtype(dtype)) return rc;
   if (B < 1 || H < 1 || W < 1) return fail(BSGP_ERR_ARG, "B, H and W must be >= 1");
   if (bh < 1 || bw < 1) return fail(BSGP_ERR_ARG, "box size (bh, bw) must be >= 1");
   if (fh < 1 || fw < 1 || fh % 2 == 0 || fw % 2 == 0)
@@ -199,17 +202,14 @@ int bsgp_background2d(const void* data, int32_t dtype, int32_t B, int32_t H, int
   // stream-ordered workspace: the call stays asynchronous
   const size_t wsb = (size_t)B * a.ws_stride * sizeof(double);
   const size_t wib = (size_t)B * (1 + 3 * ncell) * sizeof(int);
-  void* w = nullptr;
-  HIP_TRY(hipMallocAsync(&w, wsb + wib, s));
-  a.ws = static_cast<double*>(w);
-  a.wsi = reinterpret_cast<int*>(static_cast<char*>(w) + wsb);
+  StreamScratch w(s);
+  if (int rc = w.alloc(wsb + wib)) return rc;
+  a.ws = static_cast<double*>(w.p);
+  a.wsi = reinterpret_cast<int*>(static_cast<char*>(w.p) + wsb);
   hipError_t e = launch_bkg_boxstats(a, dtype == BSGP_DTYPE_F32, s);
   if (e == hipSuccess) e = launch_bkg_mesh(a, s);
   if (e == hipSuccess && (bkg_out || rms_out)) e = launch_bkg_zoom(a, s);
-  const hipError_t ef = hipFreeAsync(w, s);
-  if (e != hipSuccess) return fail(BSGP_ERR_HIP, std::string("background launch: ") + hipGetErrorString(e));
-  HIP_TRY(ef);
-  return BSGP_OK;
+  return w.finish(e, "background");
 }
 
 namespace {
@@ -228,8 +228,7 @@ int bsgp_convolve2d(const void* data, int32_t dtype, int32_t B, int32_t H, int32
   if (!data) return fail(BSGP_ERR_ARG, "data is NULL");
   if (!kernel) return fail(BSGP_ERR_ARG, "kernel is NULL");
   if (!out) return fail(BSGP_ERR_ARG, "out is NULL");
-  if (dtype != BSGP_DTYPE_F32 && dtype != BSGP_DTYPE_F64)
-    return fail(BSGP_ERR_ARG, "dtype must be BSGP_DTYPE_F32 or BSGP_DTYPE_F64");
+  if (int rc = check_dtype(dtype)) return rc;
   if (kh < 1 || kw < 1) return fail(BSGP_ERR_ARG, "kernel size (kh, kw) must be >= 1");
   if (int rc = seg_shape(B, H, W)) return rc;
   if (kh % 2 == 0 || kw % 2 == 0 || kh > kSegMaxKernel || kw > kSegMaxKernel) {
@@ -255,8 +254,7 @@ int bsgp_convolve2d_ex(const void* data, int32_t dtype, int32_t B, int32_t H, in
   if (!kernel_sum) return fail(BSGP_ERR_ARG, "kernel_sum is NULL");
   if (!out) return fail(BSGP_ERR_ARG, "out is NULL");
   if (!status_out) return fail(BSGP_ERR_ARG, "status_out is NULL");
-  if (dtype != BSGP_DTYPE_F32 && dtype != BSGP_DTYPE_F64)
-    return fail(BSGP_ERR_ARG, "dtype must be BSGP_DTYPE_F32 or BSGP_DTYPE_F64");
+  if (int rc = check_dtype(dtype)) return rc;
   if (kh < 1 || kw < 1) return fail(BSGP_ERR_ARG, "kernel size (kh, kw) must be >= 1");
   if (flags & ~(BSGP_CONV_F_FILL | BSGP_CONV_F_NORMALIZE | BSGP_CONV_F_PRESERVE_NAN))
     return fail(BSGP_ERR_ARG, "flags holds an unknown bit");
@@ -287,8 +285,7 @@ int bsgp_detect_sources(const void* data, int32_t dtype, int32_t B, int32_t H, i
                         int32_t* nlabels_out, void* stream) {
   if (!data) return fail(BSGP_ERR_ARG, "data is NULL");
   if (!labels_out || !nlabels_out) return fail(BSGP_ERR_ARG, "labels_out / nlabels_out is NULL");
-  if (dtype != BSGP_DTYPE_F32 && dtype != BSGP_DTYPE_F64)
-    return fail(BSGP_ERR_ARG, "dtype must be BSGP_DTYPE_F32 or BSGP_DTYPE_F64");
+  if (int rc = check_dtype(dtype)) return rc;
   if (npixels < 1) return fail(BSGP_ERR_ARG, "npixels must be >= 1");
   if (connectivity != 4 && connectivity != 8)
     return fail(BSGP_ERR_ARG, "connectivity must be 4 or 8");
@@ -302,16 +299,12 @@ int bsgp_detect_sources(const void* data, int32_t dtype, int32_t B, int32_t H, i
   hipStream_t s = (hipStream_t)stream;
   // stream-ordered workspace: the call stays asynchronous
   const size_t per = 2 * hw + (size_t)a.nblk;
-  void* w = nullptr;
-  HIP_TRY(hipMallocAsync(&w, (size_t)B * per * sizeof(int), s));
-  a.lab = static_cast<int*>(w);
+  StreamScratch w(s);
+  if (int rc = w.alloc((size_t)B * per * sizeof(int))) return rc;
+  a.lab = static_cast<int*>(w.p);
   a.area = a.lab + (size_t)B * hw;
   a.blk = a.area + (size_t)B * hw;
-  const hipError_t e = launch_seg_detect(a, dtype == BSGP_DTYPE_F32, s);
-  const hipError_t ef = hipFreeAsync(w, s);
-  if (e != hipSuccess) return fail(BSGP_ERR_HIP, std::string("detection launch: ") + hipGetErrorString(e));
-  HIP_TRY(ef);
-  return BSGP_OK;
+  return w.finish(launch_seg_detect(a, dtype == BSGP_DTYPE_F32, s), "detection");
 }
 
 int bsgp_segment_catalog(const double* data, const double* conv, const int32_t* labels, int32_t B,
@@ -343,8 +336,7 @@ int bsgp_segment_local_background(const void* data, int32_t dtype, const int32_t
   if (!(sigma > 0.0)) return fail(BSGP_ERR_ARG, "sigma must be > 0");
   if (maxiters < 0) return fail(BSGP_ERR_ARG, "maxiters must be >= 0");
   if (min_pixels < 1) return fail(BSGP_ERR_ARG, "min_pixels must be >= 1");
-  if (dtype != BSGP_DTYPE_F32 && dtype != BSGP_DTYPE_F64)
-    return fail(BSGP_ERR_ARG, "dtype must be BSGP_DTYPE_F32 or BSGP_DTYPE_F64");
+  if (int rc = check_dtype(dtype)) return rc;
   if (cap < 1) return fail(BSGP_ERR_ARG, "cap must be >= 1");
   if (B == 0) return BSGP_OK;  // no image: nothing to do, no pointer is followed
   if (!data) return fail(BSGP_ERR_ARG, "data is NULL");
@@ -400,9 +392,9 @@ static int deblend_sources(const double* data, const int32_t* labels, int32_t B,
   // path adds 32 bytes per pixel (one double and six ints), sized by B, H, W
   // alone and never initialised.
   const size_t rows = (size_t)B * cap, px = a.large ? (size_t)B * H * W : 0;
-  void* w = nullptr;
-  HIP_TRY(hipMallocAsync(&w, px * (sizeof(double) + 6 * sizeof(int)) + 2 * rows * sizeof(int), s));
-  a.hkey = static_cast<double*>(w);
+  StreamScratch w(s);
+  if (int rc = w.alloc(px * (sizeof(double) + 6 * sizeof(int)) + 2 * rows * sizeof(int))) return rc;
+  a.hkey = static_cast<double*>(w.p);
   a.lev = reinterpret_cast<int*>(a.hkey + px);
   a.reg = a.lev + px, a.cnt = a.reg + px, a.kept = a.cnt + px, a.mk = a.kept + px;
   a.hidx = a.mk + px;
@@ -411,10 +403,7 @@ static int deblend_sources(const double* data, const int32_t* labels, int32_t B,
   hipError_t e = hipMemsetAsync(a.nchild, 0, rows * sizeof(int), s);
   if (e == hipSuccess) e = hipMemsetAsync(status_out, 0, (size_t)B * sizeof(int), s);
   if (e == hipSuccess) e = launch_deblend(a, s);
-  const hipError_t ef = hipFreeAsync(w, s);
-  if (e != hipSuccess) return fail(BSGP_ERR_HIP, std::string("deblend launch: ") + hipGetErrorString(e));
-  HIP_TRY(ef);
-  return BSGP_OK;
+  return w.finish(e, "deblend");
 }
 
 int bsgp_deblend_sources(const double* data, const int32_t* labels, int32_t B, int32_t H, int32_t W,
@@ -514,15 +503,11 @@ int bsgp_match_catalogs(const double* x1, const double* y1, int32_t stride1, con
     return BSGP_OK;
   }
   // stream-ordered workspace: the call stays asynchronous
-  void* w = nullptr;
-  HIP_TRY(hipMallocAsync(&w, (size_t)B * rows * kMatchRowBytes, s));
-  a.ws_xy = static_cast<double*>(w);
+  StreamScratch w(s);
+  if (int rc = w.alloc((size_t)B * rows * kMatchRowBytes)) return rc;
+  a.ws_xy = static_cast<double*>(w.p);
   a.ws_state = reinterpret_cast<int*>(a.ws_xy + (size_t)B * rows * 2);
-  const hipError_t e = launch_match(a, B, false, block, s);
-  const hipError_t ef = hipFreeAsync(w, s);
-  if (e != hipSuccess) return fail(BSGP_ERR_HIP, std::string("match launch: ") + hipGetErrorString(e));
-  HIP_TRY(ef);
-  return BSGP_OK;
+  return w.finish(launch_match(a, B, false, block, s), "match");
 }
 
 int bsgp_radial_profile(const void* data, int32_t dtype, int32_t B, int32_t H, int32_t W,
@@ -531,8 +516,7 @@ int bsgp_radial_profile(const void* data, int32_t dtype, int32_t B, int32_t H, i
   if (!data) return fail(BSGP_ERR_ARG, "data is NULL");
   if (!centers) return fail(BSGP_ERR_ARG, "centers is NULL");
   if (!prof || !len) return fail(BSGP_ERR_ARG, "prof / len is NULL");
-  if (dtype != BSGP_DTYPE_F32 && dtype != BSGP_DTYPE_F64)
-    return fail(BSGP_ERR_ARG, "dtype must be BSGP_DTYPE_F32 or BSGP_DTYPE_F64");
+  if (int rc = check_dtype(dtype)) return rc;
   if (B < 1 || H < 1 || W < 1) return fail(BSGP_ERR_ARG, "B, H and W must be >= 1");
   if (rcap < 1) return fail(BSGP_ERR_ARG, "rcap must be >= 1");
   char msg[160];
@@ -595,8 +579,7 @@ int bsgp_extract_stamps(const void* img, int32_t dtype, int32_t H, int32_t W, co
                         int32_t n, int32_t sh, int32_t sw, void* out, int32_t* box_out,
                         int32_t* status_out, void* stream) {
   if (n < 0) return fail(BSGP_ERR_ARG, "n must be >= 0");
-  if (dtype != BSGP_DTYPE_F32 && dtype != BSGP_DTYPE_F64)
-    return fail(BSGP_ERR_ARG, "dtype must be BSGP_DTYPE_F32 or BSGP_DTYPE_F64");
+  if (int rc = check_dtype(dtype)) return rc;
   if (H < 1 || W < 1) return fail(BSGP_ERR_ARG, "H and W must be >= 1");
   if (sh < 1 || sw < 1) return fail(BSGP_ERR_ARG, "the stamp size (sh, sw) must be >= 1");
   if ((int64_t)sh * sw > kStampCutMaxPixels) {

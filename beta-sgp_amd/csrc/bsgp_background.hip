@@ -25,7 +25,9 @@
 
 #include <cmath>
 
-#include "bsgp_internal.hpp"
+#include "bsgp_apps.hpp"
+#include "bsgp_prims.hpp"
+#include "bsgp_reduce.hpp"
 #include "bsgp_sigclip.hpp"
 
 namespace bsgp {
@@ -71,7 +73,7 @@ __global__ void __launch_bounds__(256) k_bkg_boxstats(BkgArgs a) {
   // valid pixels, then +inf sentinels up to the power of two
   double cnt[1] = {0.0};
   for (int k = tid; k < P; k += 256) {
-    double v = bkg_inf();
+    double v = dev_inf();
     if (k < npix) {
       const int r = k / a.bw, c = k - r * a.bw;
       const int y = j * a.bh + r, x = i * a.bw + c;
@@ -93,8 +95,8 @@ __global__ void __launch_bounds__(256) k_bkg_boxstats(BkgArgs a) {
   int* wi = a.wsi + (size_t)b * (1 + 3 * (size_t)ncell) + 1;
   if ((double)(npix - nvalid) > a.excl_count || nvalid == 0) {
     if (tid == 0) {
-      raw[cell] = bkg_nan();
-      raw[ncell + cell] = bkg_nan();
+      raw[cell] = dev_nan();
+      raw[ncell + cell] = dev_nan();
       wi[cell] = 1;
       wi[ncell + cell] = 0;
       wi[2 * ncell + cell] = 0;
@@ -166,14 +168,14 @@ __global__ void __launch_bounds__(256) k_bkg_mesh(BkgArgs a) {
     if (tid == 0) st[0] = kept;
   }
   if (kept == 0) {  // every box excluded: the caller reads status[0] == 0
-    for (int c = tid; c < 4 * ncell; c += 256) ws[2 * (size_t)ncell + c] = bkg_nan();
-    if (tid < 8) scal[tid] = bkg_nan();
+    for (int c = tid; c < 4 * ncell; c += 256) ws[2 * (size_t)ncell + c] = dev_nan();
+    if (tid < 8) scal[tid] = dev_nan();
     for (int m = 0; m < 2; ++m) {
       double* mo = m == 0 ? a.mesh : a.rms_mesh;
       if (mo)
-        for (int c = tid; c < ncell; c += 256) mo[(size_t)b * ncell + c] = bkg_nan();
+        for (int c = tid; c < ncell; c += 256) mo[(size_t)b * ncell + c] = dev_nan();
     }
-    if (a.medians && tid < 2) a.medians[2 * (size_t)b + tid] = bkg_nan();
+    if (a.medians && tid < 2) a.medians[2 * (size_t)b + tid] = dev_nan();
     return;
   }
 
@@ -217,7 +219,7 @@ __global__ void __launch_bounds__(256) k_bkg_mesh(BkgArgs a) {
 
     // median filter, cells outside the mesh ignored (rank by counting)
     const int ry = a.fh / 2, rx = a.fw / 2;
-    double mn = bkg_inf(), mx = -bkg_inf();
+    double mn = dev_inf(), mx = -dev_inf();
     for (int c = tid; c < ncell; c += 256) {
       const int cy = c / nx, cx = c - cy * nx;
       const int y0 = cy - ry < 0 ? 0 : cy - ry, y1 = cy + ry > ny - 1 ? ny - 1 : cy + ry;
@@ -253,7 +255,7 @@ __global__ void __launch_bounds__(256) k_bkg_mesh(BkgArgs a) {
     int P = 1;
     while (P < ncell) P <<= 1;
     for (int c = tid; c < P; c += 256) {
-      const double u = c < ncell ? F[c] : bkg_inf();
+      const double u = c < ncell ? F[c] : dev_inf();
       A[c] = u;
       if (c < ncell) {
         filt[c] = u;

@@ -36,7 +36,8 @@
 //                       corrections are staged in LDS next to the box table.
 #include <hip/hip_runtime.h>
 
-#include "bsgp_internal.hpp"
+#include "bsgp_apps.hpp"
+#include "bsgp_prims.hpp"
 
 #pragma clang fp contract(off)
 
@@ -47,19 +48,8 @@ namespace {
 constexpr int kCoaddBlock = 256;
 constexpr int kCoaddWaves = kCoaddBlock / 64;
 
-__device__ inline double coadd_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
-
-// float64 bits -> a key that orders like the value (negatives flipped, sign bit set otherwise)
-__device__ __forceinline__ unsigned long long order_key(double d) {
-  const unsigned long long u = (unsigned long long)__double_as_longlong(d);
-  return (u >> 63) ? ~u : (u | 0x8000000000000000ULL);
-}
-__device__ __forceinline__ double order_value(unsigned long long k) {
-  const unsigned long long u = (k >> 63) ? (k & 0x7fffffffffffffffULL) : ~k;
-  return __longlong_as_double((long long)u);
-}
-
 // Workgroup sum in a fixed order; every thread gets the total.
+// (local: block_sum<1> of bsgp_reduce.hpp has a third barrier and grows k_solve_corrections' code)
 __device__ __forceinline__ double coadd_block_sum(double v, double* red) {
 #pragma unroll
   for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -84,7 +74,7 @@ __global__ void __launch_bounds__(kCoaddBlock) k_pair_offsets(CoaddOffsetArgs a)
   const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int ti = a.pairs[2 * p], tj = a.pairs[2 * p + 1];
   if (ti < 0 || ti >= a.n || tj < 0 || tj >= a.n) {  // not a pair of tiles: no offset
-    if (tid == 0) a.offsets[p] = coadd_nan();
+    if (tid == 0) a.offsets[p] = dev_nan();
     return;
   }
   const int xi = a.boxes[4 * ti], yi = a.boxes[4 * ti + 1];
@@ -95,7 +85,7 @@ __global__ void __launch_bounds__(kCoaddBlock) k_pair_offsets(CoaddOffsetArgs a)
   const int y1 = min(min(a.boxes[4 * ti + 3], a.boxes[4 * tj + 3]), min(yi, yj) + a.th);
   const int rw = x1 - x0, rh = y1 - y0;
   if (rw <= 0 || rh <= 0) {
-    if (tid == 0) a.offsets[p] = coadd_nan();
+    if (tid == 0) a.offsets[p] = dev_nan();
     return;
   }
   const unsigned int cnt = (unsigned int)rw * (unsigned int)rh;  // th * tw < 2^31 (host)
@@ -142,6 +132,7 @@ __global__ void __launch_bounds__(kCoaddBlock) k_pair_offsets(CoaddOffsetArgs a)
     __syncthreads();
     if (s_bad) break;  // (workgroup-uniform: read after the barrier)
     // the bin that holds the rank: inclusive scan of the 256 bins, one per thread
+    // (inline: block_scan of bsgp_prims.hpp adds a total and a barrier, and changes the kernel's code)
     const unsigned int h = hist[tid];
     unsigned int inc = h;
 #pragma unroll
@@ -166,7 +157,7 @@ __global__ void __launch_bounds__(kCoaddBlock) k_pair_offsets(CoaddOffsetArgs a)
   }
   if (s_bad) {  // numpy's median would be NaN: the pair leaves the graph
     if (tid == 0) {
-      a.offsets[p] = coadd_nan();
+      a.offsets[p] = dev_nan();
       atomicOr(&a.status[ti], BSGP_COADD_NONFINITE);
       atomicOr(&a.status[tj], BSGP_COADD_NONFINITE);
     }

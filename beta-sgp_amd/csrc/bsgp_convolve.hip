@@ -23,8 +23,9 @@
 // each image the bits it gets alone, and every run gives the same bits.
 #include <hip/hip_runtime.h>
 
-#include "bsgp_internal.hpp"
+#include "bsgp_apps.hpp"
 #include "bsgp_layout.hpp"
+#include "bsgp_prims.hpp"
 
 namespace bsgp {
 
@@ -42,7 +43,6 @@ constexpr size_t conv_lds_bytes(int R, int kh, int kw) {
 static_assert(conv_lds_bytes(1, kConvMaxKernel, kConvMaxKernel) <= kConvLdsMax,
               "the largest kernel's smallest tile must fit the LDS budget");
 
-__device__ __forceinline__ double conv_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
 
 // one tap of one pixel: top += v * k (and bot += k), skipped for a NaN value
 // on the interpolating path
@@ -126,7 +126,7 @@ __global__ void __launch_bounds__(256) k_conv(ConvArgs a) {
       if (rowok && gx >= 0 && gx < a.W) {
         const size_t p = (size_t)gy * a.W + gx;
         v = (double)img[p];
-        if (mask && mask[p]) v = conv_nan();
+        if (mask && mask[p]) v = dev_nan();
         if (fill_nan && v != v) v = fill;
       }
       P[ly * LW + lx] = v;
@@ -164,7 +164,7 @@ __global__ void __launch_bounds__(256) k_conv(ConvArgs a) {
     }
     const T v = img[p];
     const bool was_nan = (v != v) || (mask && mask[p]);
-    if (preserve && was_nan) o = conv_nan();
+    if (preserve && was_nan) o = dev_nan();
     left |= (o != o) && !(preserve && was_nan);
     a.out[base + p] = o;
   }

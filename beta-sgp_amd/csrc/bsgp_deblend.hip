@@ -30,7 +30,9 @@
 // result depends only on its own pixels and box.
 #include <hip/hip_runtime.h>
 
-#include "bsgp_internal.hpp"
+#include "bsgp_apps.hpp"
+#include "bsgp_prims.hpp"
+#include "bsgp_reduce.hpp"
 
 namespace bsgp {
 
@@ -40,39 +42,9 @@ constexpr int kBox = kDeblendMaxBox;
 constexpr int kOutside = -1;  // not a pixel of the parent
 constexpr int kFree = -2;     // a pixel of the parent in no region / not yet flooded
 
-__device__ __forceinline__ double db_inf() { return __longlong_as_double(0x7ff0000000000000LL); }
-
-__device__ __forceinline__ int db_load(const int* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-
-// seg_find / seg_unite of bsgp_segment.hip on an LDS array
-__device__ __forceinline__ int db_find(int* L, int a) {
-  int p = db_load(L + a);
-  while (p != a) {
-    const int g = db_load(L + p);
-    if (g != p) atomicMin(L + a, g);
-    a = p;
-    p = g;
-  }
-  return a;
-}
-
-__device__ __forceinline__ void db_unite(int* L, int a, int b) {
-  for (;;) {
-    a = db_find(L, a);
-    b = db_find(L, b);
-    if (a == b) return;
-    if (a < b) {
-      const int t = a;
-      a = b;
-      b = t;
-    }
-    const int old = atomicMin(L + a, b);
-    if (old == a) return;
-    a = old;
-  }
-}
+// scope of the union-find's loads: k_deblend_parent's array is in LDS,
+// k_deblend_large's in global memory
+constexpr int kLds = __HIP_MEMORY_SCOPE_WORKGROUP, kAgent = __HIP_MEMORY_SCOPE_AGENT;
 
 // a table of kBox 16-bit counters, two per int (a count is at most kBox)
 __device__ __forceinline__ void t16_add(int* t, int i) { atomicAdd(t + (i >> 1), 1 << ((i & 1) << 4)); }
@@ -170,29 +142,6 @@ __device__ __forceinline__ double db_wave_sum_of(const double* v, const int* lab
   return wave_sum(s);
 }
 
-// the workgroup scan of bsgp_segment.hip
-__device__ __forceinline__ int db_block_scan(int c, int* wsum, int* total) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int inc = c;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int u = __shfl_up(inc, o, 64);
-    if (lane >= o) inc += u;
-  }
-  if (lane == 63) wsum[w] = inc;
-  __syncthreads();
-  int base = 0, tot = 0;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int u = wsum[k];
-    if (k < w) base += u;
-    tot += u;
-  }
-  __syncthreads();
-  *total = tot;
-  return base + inc - c;
-}
-
 __device__ __forceinline__ int db_rows(const DeblendArgs& a, int b) {
   const int m = a.nlabels[b];
   return m < a.cap ? (m < 0 ? 0 : m) : a.cap;
@@ -245,7 +194,7 @@ __global__ void __launch_bounds__(256) k_deblend_parent(DeblendArgs a) {
 
   // D1
   if (wave == 0) {
-    double s = 0.0, mn = db_inf(), mx = -db_inf();
+    double s = 0.0, mn = dev_inf(), mx = -dev_inf();
     for (int k = lane; k < n; k += 64) {
       if (reg[k] == kOutside) continue;
       const double x = v[k];
@@ -289,29 +238,29 @@ __global__ void __launch_bounds__(256) k_deblend_parent(DeblendArgs a) {
     // level, and the levels rise: nothing can split from here on
     if (sint[5] < 2 * (long long)a.npixels) break;
     for (int p = tid; p < n; p += 256) {
-      if (db_load(lev + p) < 0) continue;
+      if (uf_load<kLds>(lev + p) < 0) continue;
       const int y = p / bw, x = p - y * bw, q = p - bw;
-      const bool w = x > 0 && db_load(lev + p - 1) >= 0;
-      const bool nn = y > 0 && db_load(lev + q) >= 0;
+      const bool w = x > 0 && uf_load<kLds>(lev + p - 1) >= 0;
+      const bool nn = y > 0 && uf_load<kLds>(lev + q) >= 0;
       if (a.conn == 4) {
-        if (w) db_unite(lev, p, p - 1);
-        if (nn) db_unite(lev, p, q);
+        if (w) uf_unite<kLds>(lev, p, p - 1);
+        if (nn) uf_unite<kLds>(lev, p, q);
         continue;
       }
       if (nn) {
-        db_unite(lev, p, q);
+        uf_unite<kLds>(lev, p, q);
         continue;
       }
-      const bool nw = y > 0 && x > 0 && db_load(lev + q - 1) >= 0;
-      const bool ne = y > 0 && x < bw - 1 && db_load(lev + q + 1) >= 0;
-      if (ne) db_unite(lev, p, q + 1);
-      if (nw) db_unite(lev, p, q - 1);
-      else if (w) db_unite(lev, p, p - 1);
+      const bool nw = y > 0 && x > 0 && uf_load<kLds>(lev + q - 1) >= 0;
+      const bool ne = y > 0 && x < bw - 1 && uf_load<kLds>(lev + q + 1) >= 0;
+      if (ne) uf_unite<kLds>(lev, p, q + 1);
+      if (nw) uf_unite<kLds>(lev, p, q - 1);
+      else if (w) uf_unite<kLds>(lev, p, p - 1);
     }
     __syncthreads();
     for (int p = tid; p < n; p += 256) {
-      if (db_load(lev + p) < 0) continue;
-      const int r = db_find(lev, p);
+      if (uf_load<kLds>(lev + p) < 0) continue;
+      const int r = uf_find<kLds>(lev, p);
       if (r != p) __hip_atomic_store(lev + p, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
       t16_add(bufA, r);
     }
@@ -359,7 +308,7 @@ __global__ void __launch_bounds__(256) k_deblend_parent(DeblendArgs a) {
       sint[3] = 0;
     }
     __syncthreads();
-    double bf = db_inf();
+    double bf = dev_inf();
     int bc = 0x7fffffff, below = 0;
     for (int ci = wave; ci < nm; ci += 4) {
       const int c = mk[ci];
@@ -425,40 +374,10 @@ namespace {
 constexpr int kHeapLds = 5120;               // heap entries in LDS: the heap's first levels
 constexpr int kAccSlots = kHeapLds / 64 / 4;  // D6: children one wave sums in one pass over the box
 
-// the arrays integer atomics write are read at the scope of those atomics
-__device__ __forceinline__ int gl_load(const int* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
+// the arrays integer atomics write are read (uf_load<kAgent>) and written at the
+// scope of those atomics
 __device__ __forceinline__ void gl_store(int* p, int v) {
   __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// seg_find / seg_unite of bsgp_segment.hip
-__device__ __forceinline__ int gl_find(int* L, int a) {
-  int p = gl_load(L + a);
-  while (p != a) {
-    const int g = gl_load(L + p);
-    if (g != p) atomicMin(L + a, g);
-    a = p;
-    p = g;
-  }
-  return a;
-}
-
-__device__ __forceinline__ void gl_unite(int* L, int a, int b) {
-  for (;;) {
-    a = gl_find(L, a);
-    b = gl_find(L, b);
-    if (a == b) return;
-    if (a < b) {
-      const int t = a;
-      a = b;
-      b = t;
-    }
-    const int old = atomicMin(L + a, b);
-    if (old == a) return;
-    a = old;
-  }
 }
 
 // The flood's heap: entries (value, pixel) in db_before's order, the key inside
@@ -592,7 +511,7 @@ __global__ void __launch_bounds__(256) k_deblend_large(DeblendArgs a) {
 
   // D1
   if (wave == 0) {
-    double s = 0.0, mn = db_inf(), mx = -db_inf();
+    double s = 0.0, mn = dev_inf(), mx = -dev_inf();
     for (int k = lane; k < n; k += 64) {
       const int q = bx.pix(k);
       if (labs[q] != want) continue;
@@ -636,29 +555,30 @@ __global__ void __launch_bounds__(256) k_deblend_large(DeblendArgs a) {
     if (sint[5] < 2 * (long long)a.npixels) break;
     for (int k = tid; k < n; k += 256) {
       const int y = k / bw, x = k - y * bw, p = (y0 + y) * a.W + x0 + x, q = p - a.W;
-      if (labs[p] != want || gl_load(lev + p) < 0) continue;
-      const bool w = x > 0 && labs[p - 1] == want && gl_load(lev + p - 1) >= 0;
-      const bool nn = y > 0 && labs[q] == want && gl_load(lev + q) >= 0;
+      if (labs[p] != want || uf_load<kAgent>(lev + p) < 0) continue;
+      const bool w = x > 0 && labs[p - 1] == want && uf_load<kAgent>(lev + p - 1) >= 0;
+      const bool nn = y > 0 && labs[q] == want && uf_load<kAgent>(lev + q) >= 0;
       if (a.conn == 4) {
-        if (w) gl_unite(lev, p, p - 1);
-        if (nn) gl_unite(lev, p, q);
+        if (w) uf_unite<kAgent>(lev, p, p - 1);
+        if (nn) uf_unite<kAgent>(lev, p, q);
         continue;
       }
       if (nn) {
-        gl_unite(lev, p, q);
+        uf_unite<kAgent>(lev, p, q);
         continue;
       }
-      const bool nw = y > 0 && x > 0 && labs[q - 1] == want && gl_load(lev + q - 1) >= 0;
-      const bool ne = y > 0 && x < bw - 1 && labs[q + 1] == want && gl_load(lev + q + 1) >= 0;
-      if (ne) gl_unite(lev, p, q + 1);
-      if (nw) gl_unite(lev, p, q - 1);
-      else if (w) gl_unite(lev, p, p - 1);
+      const bool nw = y > 0 && x > 0 && labs[q - 1] == want && uf_load<kAgent>(lev + q - 1) >= 0;
+      const bool ne =
+          y > 0 && x < bw - 1 && labs[q + 1] == want && uf_load<kAgent>(lev + q + 1) >= 0;
+      if (ne) uf_unite<kAgent>(lev, p, q + 1);
+      if (nw) uf_unite<kAgent>(lev, p, q - 1);
+      else if (w) uf_unite<kAgent>(lev, p, p - 1);
     }
     __syncthreads();
     for (int k = tid; k < n; k += 256) {
       const int p = bx.pix(k);
-      if (labs[p] != want || gl_load(lev + p) < 0) continue;
-      const int r = gl_find(lev, p);
+      if (labs[p] != want || uf_load<kAgent>(lev + p) < 0) continue;
+      const int r = uf_find<kAgent>(lev, p);
       if (r != p) gl_store(lev + p, r);
       atomicAdd(cnt + r, 1);
     }
@@ -667,7 +587,7 @@ __global__ void __launch_bounds__(256) k_deblend_large(DeblendArgs a) {
     for (int k = tid; k < n; k += 256) {
       const int p = bx.pix(k);
       if (labs[p] != want) continue;
-      if (gl_load(lev + p) == p && gl_load(cnt + p) >= a.npixels && reg[p] >= 0)
+      if (uf_load<kAgent>(lev + p) == p && uf_load<kAgent>(cnt + p) >= a.npixels && reg[p] >= 0)
         atomicAdd(kept + reg[p], 1);
     }
     __syncthreads();
@@ -675,9 +595,9 @@ __global__ void __launch_bounds__(256) k_deblend_large(DeblendArgs a) {
       const int p = bx.pix(k);
       if (labs[p] != want) continue;
       const int R = reg[p];
-      if (R < 0 || gl_load(kept + R) < 2) continue;
-      const int l = gl_load(lev + p);
-      reg[p] = (l >= 0 && gl_load(cnt + l) >= a.npixels) ? l : kFree;
+      if (R < 0 || uf_load<kAgent>(kept + R) < 2) continue;
+      const int l = uf_load<kAgent>(lev + p);
+      reg[p] = (l >= 0 && uf_load<kAgent>(cnt + l) >= a.npixels) ? l : kFree;
       sint[1] = 1;
     }
     __syncthreads();
@@ -781,7 +701,7 @@ __global__ void __launch_bounds__(256) k_deblend_large(DeblendArgs a) {
     __syncthreads();
     // every child's fraction: a wave takes kAccSlots children per pass over the
     // box, lane partials in box raster order with stride 64 (db_wave_sum_of's sums)
-    double bf = db_inf();
+    double bf = dev_inf();
     int bc = 0x7fffffff, below = 0;
     double* acc = lk + wave * (kAccSlots * 64);
     for (int base = wave * kAccSlots; base < nm; base += 4 * kAccSlots) {
@@ -792,7 +712,7 @@ __global__ void __launch_bounds__(256) k_deblend_large(DeblendArgs a) {
         if (labs[p] != want) continue;
         const int l = fl[p];
         if (l < 0) continue;
-        const int s = gl_load(kept + l) - base;
+        const int s = uf_load<kAgent>(kept + l) - base;
         if (s >= 0 && s < ng) acc[s * 64 + lane] += dat[p];
       }
       for (int s = 0; s < ng; ++s) {
@@ -843,7 +763,7 @@ __global__ void __launch_bounds__(256) k_deblend_large(DeblendArgs a) {
     const int p = bx.pix(k);
     if (labs[p] != want) continue;
     const int l = fl[p];
-    fl[p] = l >= 0 ? gl_load(kept + l) : -1;
+    fl[p] = l >= 0 ? uf_load<kAgent>(kept + l) : -1;
   }
   if (tid == 0) a.nchild[row] = alive;
 }
@@ -860,7 +780,7 @@ __global__ void __launch_bounds__(256) k_deblend_number(DeblendArgs a) {
     const int c = valid ? a.nchild[row0 + i] : 0;
     const int u = valid && c == 0;
     int tu, tc;
-    const int eu = db_block_scan(u, wsum, &tu), ec = db_block_scan(c, wsum, &tc);
+    const int eu = block_scan(u, wsum, &tu), ec = block_scan(c, wsum, &tc);
     if (i < n) a.base[row0 + i] = !valid ? 0 : (u ? cu + eu + 1 : cc + ec);
     cu += tu;
     cc += tc;

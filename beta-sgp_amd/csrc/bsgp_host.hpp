@@ -1,6 +1,6 @@
 // bsgp_host.hpp — private to the C-ABI host layer (bsgp_plan.hip, bsgp_solve.hip,
-// bsgp_apps.hip): error reporting, the device scope, owning device buffers and
-// the plan.  Host only; no kernel unit includes it.
+// bsgp_apps.hip): error reporting, the device scope, owning device buffers, the
+// stream-ordered scratch of one call and the plan.  Host only; no kernel unit includes it.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -8,6 +8,7 @@
 #include <string>
 #include <utility>
 
+#include "bsgp_apps.hpp"
 #include "bsgp_internal.hpp"
 #include "bsgp_layout.hpp"
 
@@ -91,6 +92,39 @@ struct HostWord {
     if (p) (void)hipHostFree(p);
   }
   hipError_t alloc(unsigned flags) { return hipHostMalloc(&p, 256, flags); }
+};
+
+// The stream-ordered workspace of one entry point: allocated on the caller's
+// stream and freed on it on every exit, so the call stays asynchronous and no
+// path leaks.  alloc and finish return BSGP_OK or the failure they reported.
+struct StreamScratch {
+  void* p = nullptr;
+  hipStream_t s;
+  explicit StreamScratch(hipStream_t stream) : s(stream) {}
+  StreamScratch(const StreamScratch&) = delete;
+  StreamScratch& operator=(const StreamScratch&) = delete;
+  ~StreamScratch() { (void)release(); }
+  int alloc(size_t bytes) {
+    const hipError_t e = hipMallocAsync(&p, bytes, s);
+    if (e == hipSuccess) return BSGP_OK;
+    p = nullptr;
+    return fail(BSGP_ERR_HIP, "hipMallocAsync(" + std::to_string(bytes) + " bytes of workspace): " +
+                                  hipGetErrorString(e));
+  }
+  hipError_t release() {
+    const hipError_t e = p ? hipFreeAsync(p, s) : hipSuccess;
+    p = nullptr;
+    return e;
+  }
+  // after the launches: frees, and reports the launches' error e as
+  // "<what> launch: ..." in preference to the free's
+  int finish(hipError_t e, const char* what) {
+    const hipError_t ef = release();
+    if (e != hipSuccess)
+      return fail(BSGP_ERR_HIP, std::string(what) + " launch: " + hipGetErrorString(e));
+    HIP_TRY(ef);
+    return BSGP_OK;
+  }
 };
 
 }  // namespace bsgp

@@ -21,7 +21,9 @@
 
 #include <cmath>
 
-#include "bsgp_internal.hpp"
+#include "bsgp_apps.hpp"
+#include "bsgp_prims.hpp"
+#include "bsgp_reduce.hpp"
 #include "bsgp_sigclip.hpp"
 
 namespace bsgp {
@@ -117,7 +119,7 @@ __global__ void __launch_bounds__(256) k_localbkg(LocalBkgArgs a, int lds_min, i
   }
   int P = 1;
   while (P < n) P <<= 1;
-  for (int k = n + tid; k < P; k += 256) s[k] = bkg_inf();
+  for (int k = n + tid; k < P; k += 256) s[k] = dev_inf();
   __syncthreads();
   bkg_sort(s, P);
 

@@ -23,7 +23,8 @@
 // coordinates on the left.
 #include <hip/hip_runtime.h>
 
-#include "bsgp_internal.hpp"
+#include "bsgp_apps.hpp"
+#include "bsgp_prims.hpp"
 
 #pragma clang fp contract(off)
 
@@ -31,7 +32,6 @@ namespace bsgp {
 
 namespace {
 
-__device__ inline double match_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
 
 __device__ __forceinline__ double match_d2(const double2 p, const double2 q) {
   const double dx = p.x - q.x, dy = p.y - q.y;
@@ -44,7 +44,7 @@ __device__ __forceinline__ int match_stage(const MatchCat& c, int b, int n, int 
   int st = 0;
   for (int r = lo + tid; r < hi; r += nt) {
     const int i = r - lo;
-    double2 p{match_nan(), match_nan()};
+    double2 p{dev_nan(), dev_nan()};
     if (i < n) {
       const size_t e = (size_t)b * c.cap + i;
       if (!c.valid || c.valid[e * c.vstride] > 0) {
@@ -90,7 +90,7 @@ __global__ void __launch_bounds__(1024) k_match(MatchArgs a) {
   st |= match_stage(a.c1, b, n1, 0, R1, tid, nt, xy, best, match);
   st |= match_stage(a.c2, b, n2, R1, rows, tid, nt, xy, best, match);
   double* sep1 = a.sep1 + (size_t)b * a.c1.cap;
-  for (int i = tid; i < a.c1.cap; i += nt) sep1[i] = match_nan();  // row i's lane also accepts it
+  for (int i = tid; i < a.c1.cap; i += nt) sep1[i] = dev_nan();  // row i's lane also accepts it
   __syncthreads();
   if (st) atomicOr(&s_status, st);
 
@@ -126,8 +126,8 @@ __global__ void __launch_bounds__(1024) k_match(MatchArgs a) {
       sep1[i] = __dsqrt_rn(match_d2(xy[i], xy[R1 + j]));
       match[i] = j;
       match[R1 + j] = i;
-      xy[i].x = match_nan();
-      xy[R1 + j].x = match_nan();
+      xy[i].x = dev_nan();
+      xy[R1 + j].x = dev_nan();
       acc = 1;
       ++mine;
     }

@@ -11,7 +11,7 @@
 // exp(): tiny next to a solve; the point is removing the host round trip.
 #include <hip/hip_runtime.h>
 
-#include "bsgp_internal.hpp"
+#include "bsgp_apps.hpp"
 #include "bsgp_psf.hpp"
 
 namespace bsgp {

@@ -8,13 +8,14 @@
 // stamp is normalised by its numpy sum (normalize_psf_mat, :129-137).
 //
 // Everything here follows the reference's operation order (no FMA contraction
-// in the build), and the normalising sum is numpy's pairwise summation, so a
-// stamp differs from the reference's only by the exp() implementation.
+// in the build), and the normalising sum is numpy's pairwise summation
+// (np_pairwise_sum, bsgp_prims.hpp), so a stamp differs from the reference's
+// only by the exp() implementation.
 #pragma once
 
 #include <cmath>
 
-#include "bsgp_fft.hpp"  // BSGP_HD
+#include "bsgp_prims.hpp"  // BSGP_HD, np_pairwise_sum
 
 namespace bsgp {
 
@@ -73,64 +74,6 @@ BSGP_HD double psf_pix(const PsfModel& M, const Coef& loc, double x, double y) {
     rr *= M.sig2;
   }
   return pix;
-}
-
-// numpy's pairwise summation of a contiguous double array (what np.sum does
-// for the 31x31 stamp): blocks of <= 128 with 8 accumulators, halves split at
-// a multiple of 8, evaluated left half first.  Iterative (explicit stack).
-BSGP_HD double np_pairwise_block(const double* a, int n) {
-  if (n < 8) {
-    double r = 0.0;
-    for (int i = 0; i < n; ++i) r += a[i];
-    return r;
-  }
-  double r[8];
-  for (int j = 0; j < 8; ++j) r[j] = a[j];
-  int i = 8;
-  for (; i < n - (n % 8); i += 8)
-    for (int j = 0; j < 8; ++j) r[j] += a[i + j];
-  double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-  for (; i < n; ++i) res += a[i];
-  return res;
-}
-
-BSGP_HD double np_pairwise_sum(const double* a, int n) {
-  int off[40], len[40], stage[40];
-  double left[40];
-  int sp = 0;
-  off[0] = 0;
-  len[0] = n;
-  stage[0] = 0;
-  double ret = 0.0;
-  for (;;) {
-    if (len[sp] > 128 && stage[sp] == 0) {  // descend into the left half
-      int n2 = len[sp] / 2;
-      n2 -= n2 % 8;
-      stage[sp] = 1;
-      off[sp + 1] = off[sp];
-      len[sp + 1] = n2;
-      stage[sp + 1] = 0;
-      ++sp;
-      continue;
-    }
-    ret = np_pairwise_block(a + off[sp], len[sp]);
-    for (;;) {  // hand `ret` up the stack
-      if (sp == 0) return ret;
-      --sp;
-      if (stage[sp] == 1) {  // left half done: evaluate the right half
-        left[sp] = ret;
-        stage[sp] = 2;
-        int n2 = len[sp] / 2;
-        n2 -= n2 % 8;
-        off[sp + 1] = off[sp] + n2;
-        len[sp + 1] = len[sp] - n2;
-        stage[sp + 1] = 0;
-        ++sp;
-        break;
-      }
-      ret = left[sp] + ret;
-    }
-  }
 }
 
 }  // namespace bsgp

@@ -30,113 +30,14 @@
 // matter (min, max, count): a batch gives each image the bits it gets alone.
 #include <hip/hip_runtime.h>
 
-#include "bsgp_internal.hpp"
+#include "bsgp_apps.hpp"
+#include "bsgp_prims.hpp"
+#include "bsgp_reduce.hpp"
 
 namespace bsgp {
 
 namespace {
-
-__device__ __forceinline__ double seg_inf() { return __longlong_as_double(0x7ff0000000000000LL); }
-
-__device__ __forceinline__ int seg_load(const int* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// root of a: parents never increase along a path, so the walk ends.  On the
-// way every visited pixel is moved to its grandparent (path halving; an
-// atomicMin, since a concurrent link may already have moved it further up).
-__device__ __forceinline__ int seg_find(int* L, int a) {
-  int p = seg_load(L + a);
-  while (p != a) {
-    const int g = seg_load(L + p);
-    if (g != p) atomicMin(L + a, g);
-    a = p;
-    p = g;
-  }
-  return a;
-}
-
-// unite the components of a and b: link the larger root to the smaller.  If
-// another thread linked that root first (old != a), its link target and b are
-// united instead, so no union is lost; both roots only ever decrease.
-__device__ __forceinline__ void seg_unite(int* L, int a, int b) {
-  for (;;) {
-    a = seg_find(L, a);
-    b = seg_find(L, b);
-    if (a == b) return;
-    if (a < b) {
-      const int t = a;
-      a = b;
-      b = t;
-    }
-    const int old = atomicMin(L + a, b);
-    if (old == a) return;
-    a = old;
-  }
-}
-
-// min / max of one int per lane over the wave, in every lane
-__device__ __forceinline__ int seg_wave_min(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const int u = __shfl_xor(v, o, 64);
-    v = u < v ? u : v;
-  }
-  return v;
-}
-__device__ __forceinline__ int seg_wave_max(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const int u = __shfl_xor(v, o, 64);
-    v = u > v ? u : v;
-  }
-  return v;
-}
-
-// exclusive prefix of one count per thread over the 256-thread workgroup, in
-// thread order; *total is the workgroup's sum (in every thread)
-__device__ __forceinline__ int seg_block_scan(int c, int* wsum, int* total) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int inc = c;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int u = __shfl_up(inc, o, 64);
-    if (lane >= o) inc += u;
-  }
-  if (lane == 63) wsum[w] = inc;
-  __syncthreads();
-  int base = 0, tot = 0;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int u = wsum[k];
-    if (k < w) base += u;
-    tot += u;
-  }
-  __syncthreads();
-  *total = tot;
-  return base + inc - c;
-}
-
-// numpy's float64 np.sum of n <= 128 contiguous values (one pairwise leaf):
-// a plain loop below 8, else 8 strided accumulators folded as
-// ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)) and the remainder added
-__device__ __forceinline__ double seg_numpy_sum(const double* v, int n) {
-  if (n < 8) {
-    double s = 0.0;
-    for (int i = 0; i < n; ++i) s += v[i];
-    return s;
-  }
-  double r0 = v[0], r1 = v[1], r2 = v[2], r3 = v[3], r4 = v[4], r5 = v[5], r6 = v[6], r7 = v[7];
-  int i = 8;
-  for (; i < n - (n % 8); i += 8) {
-    r0 += v[i], r1 += v[i + 1], r2 += v[i + 2], r3 += v[i + 3];
-    r4 += v[i + 4], r5 += v[i + 5], r6 += v[i + 6], r7 += v[i + 7];
-  }
-  double s = ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7));
-  for (; i < n; ++i) s += v[i];
-  return s;
-}
-
+constexpr int kAgent = __HIP_MEMORY_SCOPE_AGENT;  // the union-find lives in global memory
 }  // namespace
 
 // -------------------------------------------------------------- convolution
@@ -146,7 +47,7 @@ __global__ void __launch_bounds__(256) k_seg_convolve(SegConvArgs a) {
   const int nk = a.kh * a.kw;
   if ((int)threadIdx.x < nk) K[threadIdx.x] = a.kernel[threadIdx.x];
   __syncthreads();
-  if (threadIdx.x == 0) K[nk] = seg_numpy_sum(K, nk);
+  if (threadIdx.x == 0) K[nk] = np_pairwise_block(K, nk);
   __syncthreads();
   const double ksum = K[nk];
   const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y, b = blockIdx.z;
@@ -197,28 +98,28 @@ __global__ void __launch_bounds__(256) k_seg_union(SegArgs a) {
   if (pu >= (unsigned)hw) return;
   const int p = (int)pu, b = blockIdx.y;
   int* L = a.lab + (size_t)b * hw;
-  if (seg_load(L + p) < 0) return;
+  if (uf_load<kAgent>(L + p) < 0) return;
   const int y = p / a.W, x = p - y * a.W;
-  const bool w = x > 0 && seg_load(L + p - 1) >= 0;
+  const bool w = x > 0 && uf_load<kAgent>(L + p - 1) >= 0;
   const int q = p - a.W;  // the pixel above
-  const bool n = y > 0 && seg_load(L + q) >= 0;
+  const bool n = y > 0 && uf_load<kAgent>(L + q) >= 0;
   if (a.conn == 4) {
-    if (w) seg_unite(L, p, p - 1);
-    if (n) seg_unite(L, p, q);
+    if (w) uf_unite<kAgent>(L, p, p - 1);
+    if (n) uf_unite<kAgent>(L, p, q);
     return;
   }
   // connectivity 8: W, NW and NE all touch N, and those contacts are united
   // by N's, NE's and W's own threads, so with N one union is enough; without
   // N, NE still has to be joined with NW or W (Wu, Otoo and Suzuki's tree)
   if (n) {
-    seg_unite(L, p, q);
+    uf_unite<kAgent>(L, p, q);
     return;
   }
-  const bool nw = y > 0 && x > 0 && seg_load(L + q - 1) >= 0;
-  const bool ne = y > 0 && x < a.W - 1 && seg_load(L + q + 1) >= 0;
-  if (ne) seg_unite(L, p, q + 1);
-  if (nw) seg_unite(L, p, q - 1);
-  else if (w) seg_unite(L, p, p - 1);
+  const bool nw = y > 0 && x > 0 && uf_load<kAgent>(L + q - 1) >= 0;
+  const bool ne = y > 0 && x < a.W - 1 && uf_load<kAgent>(L + q + 1) >= 0;
+  if (ne) uf_unite<kAgent>(L, p, q + 1);
+  if (nw) uf_unite<kAgent>(L, p, q - 1);
+  else if (w) uf_unite<kAgent>(L, p, p - 1);
 }
 
 __global__ void __launch_bounds__(256) k_seg_flatten(SegArgs a) {
@@ -226,10 +127,10 @@ __global__ void __launch_bounds__(256) k_seg_flatten(SegArgs a) {
   const unsigned pu = blockIdx.x * 256u + threadIdx.x;
   int* L = a.lab + (size_t)b * hw;
   const int p = (int)pu;
-  const bool det = pu < (unsigned)hw && seg_load(L + p) >= 0;
+  const bool det = pu < (unsigned)hw && uf_load<kAgent>(L + p) >= 0;
   int r = -1;
   if (det) {
-    r = seg_find(L, p);
+    r = uf_find<kAgent>(L, p);
     // a root keeps its own index; any other pixel's parent only moves up its path
     if (r != p) __hip_atomic_store(L + p, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
@@ -273,7 +174,7 @@ __global__ void __launch_bounds__(256) k_seg_count(SegArgs a) {
   unsigned bits;
   const int c = seg_flags(a, b, blockIdx.x * (unsigned)kSegChunk + threadIdx.x * 8u, &bits);
   int total;
-  (void)seg_block_scan(c, wsum, &total);
+  (void)block_scan(c, wsum, &total);
   if (threadIdx.x == 0) a.blk[(size_t)b * a.nblk + blockIdx.x] = total;
 }
 
@@ -287,7 +188,7 @@ __global__ void __launch_bounds__(256) k_seg_scan(SegArgs a) {
     const int i = base + threadIdx.x;
     const int c = i < a.nblk ? blk[i] : 0;
     int total;
-    const int ex = seg_block_scan(c, wsum, &total);
+    const int ex = block_scan(c, wsum, &total);
     if (i < a.nblk) blk[i] = carry + ex;
     carry += total;
   }
@@ -302,7 +203,7 @@ __global__ void __launch_bounds__(256) k_seg_assign(SegArgs a) {
   unsigned bits;
   const int c = seg_flags(a, b, p0, &bits);
   int total;
-  int rank = a.blk[(size_t)b * a.nblk + blockIdx.x] + seg_block_scan(c, wsum, &total);
+  int rank = a.blk[(size_t)b * a.nblk + blockIdx.x] + block_scan(c, wsum, &total);
   const int* L = a.lab + (size_t)b * hw;
   int* A = a.area + (size_t)b * hw;
 #pragma unroll
@@ -381,8 +282,8 @@ __global__ void __launch_bounds__(256) k_cat_bbox(SegCatArgs a) {
   const int first = __ffsll((long long)m) - 1;
   const int l0 = __shfl(l, first, 64);
   const bool same = __ballot(valid && l != l0) == 0;
-  const int xmn = seg_wave_min(valid ? x : 0x7fffffff), xmx = seg_wave_max(valid ? x : -1);
-  const int ymn = seg_wave_min(valid ? y : 0x7fffffff), ymx = seg_wave_max(valid ? y : -1);
+  const int xmn = wave_min(valid ? x : 0x7fffffff), xmx = wave_max(valid ? x : -1);
+  const int ymn = wave_min(valid ? y : 0x7fffffff), ymx = wave_max(valid ? y : -1);
   if (same) {
     if ((int)(threadIdx.x & 63) == first) {
       int* ic = a.icols + ((size_t)b * a.cap + (l0 - 1)) * 5;
@@ -417,7 +318,7 @@ __global__ void __launch_bounds__(256) k_cat_measure(SegCatArgs a) {
   const double* cnv = (a.conv ? a.conv : a.data) + o;
   const int want = sgm + 1;
 
-  double flux = 0.0, mn = seg_inf(), mx = -seg_inf(), sc = 0.0, sx = 0.0, sy = 0.0;
+  double flux = 0.0, mn = dev_inf(), mx = -dev_inf(), sc = 0.0, sx = 0.0, sy = 0.0;
   for (int k = lane; k < n; k += 64) {
     const int r = k / bw, c = k - r * bw;
     const size_t q = (size_t)(y0 + r) * a.W + (x0 + c);

@@ -8,12 +8,10 @@
 
 #include <cmath>
 
-#include "bsgp_device.hpp"
+#include "bsgp_prims.hpp"
+#include "bsgp_reduce.hpp"
 
 namespace bsgp {
-
-__device__ __forceinline__ double bkg_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
-__device__ __forceinline__ double bkg_inf() { return __longlong_as_double(0x7ff0000000000000LL); }
 
 // ascending bitonic sort of s[0, P) in LDS, P a power of two, 256 threads
 __device__ __forceinline__ void bkg_sort(double* s, int P) {
@@ -80,7 +78,7 @@ __device__ __forceinline__ SigClip sigma_clip_sorted(const double* s, int nvalid
     ++it;
     if (nhi <= nlo) {  // a sigma so small that nothing is left: NaN, as numpy of no values
       lo = hi = nlo;
-      med = mean = sd = bkg_nan();
+      med = mean = sd = dev_nan();
       break;
     }
     const bool changed = nlo != lo || nhi != hi;

@@ -19,8 +19,9 @@
 // an image gets the bits it gets alone.
 #include <hip/hip_runtime.h>
 
-#include "bsgp_device.hpp"
-#include "bsgp_internal.hpp"
+#include "bsgp_apps.hpp"
+#include "bsgp_prims.hpp"
+#include "bsgp_reduce.hpp"
 
 #define LM_FN __device__ __forceinline__
 #define LM_LANE ((int)threadIdx.x)
@@ -35,16 +36,6 @@ namespace bsgp {
 namespace {
 
 constexpr int kTile = 256;  // pixels staged per round of k_radprof
-
-__device__ __forceinline__ double stamps_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
-
-__device__ __forceinline__ int wave_max_int(int v) {
-  for (int o = 32; o > 0; o >>= 1) {
-    const int u = __shfl_xor(v, o, 64);
-    v = u > v ? u : v;
-  }
-  return v;
-}
 
 // NCH: bins per lane (bin = lane + 64 c); rcap <= 64 NCH
 template <int NCH, typename T>
@@ -86,14 +77,14 @@ __global__ void __launch_bounds__(64) k_radprof(StampProfArgs a) {
         if (k == lane + 64 * c) acc[c] += v, ++cnt[c];
     }
   }
-  kmax = wave_max_int(kmax);
+  kmax = wave_max(kmax);
   const int len = kmax + 1;
   if (lane == 0) a.len[b] = len;
   double* out = a.prof + (size_t)b * a.rcap;
 #pragma unroll
   for (int c = 0; c < NCH; ++c) {
     const int k = lane + 64 * c;
-    if (k < a.rcap) out[k] = k < len ? acc[c] / (double)cnt[c] : stamps_nan();
+    if (k < a.rcap) out[k] = k < len ? acc[c] / (double)cnt[c] : dev_nan();
   }
 }
 
@@ -126,12 +117,12 @@ __global__ void __launch_bounds__(64) k_w1(StampW1Args a) {
   const int b = blockIdx.x, lane = threadIdx.x;
   const int n = a.ulen ? a.ulen[b] : a.rcap, m = a.vlen ? a.vlen[b] : a.rcap;
   if (n < 1 || m < 1 || n > a.rcap || m > a.rcap) {
-    if (lane == 0) a.out[b] = stamps_nan();
+    if (lane == 0) a.out[b] = dev_nan();
     return;
   }
   const double* u = a.u + (size_t)b * a.rcap;
   const double* v = a.v + (size_t)b * a.rcap;
-  const double inf = __longlong_as_double(0x7ff0000000000000LL);
+  const double inf = dev_inf();
   int bad = 0;
   for (int i = lane; i < a.P; i += 64) {
     double x = inf;
@@ -142,9 +133,9 @@ __global__ void __launch_bounds__(64) k_w1(StampW1Args a) {
     val[i] = x;
     tag[i] = t;
   }
-  bad = wave_max_int(bad);
+  bad = wave_max(bad);
   if (bad) {
-    if (lane == 0) a.out[b] = stamps_nan();
+    if (lane == 0) a.out[b] = dev_nan();
     return;
   }
   wave_sync();

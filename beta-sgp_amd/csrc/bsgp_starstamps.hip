@@ -21,7 +21,8 @@
 // for bit.
 #include <hip/hip_runtime.h>
 
-#include "bsgp_internal.hpp"
+#include "bsgp_apps.hpp"
+#include "bsgp_prims.hpp"
 
 #pragma clang fp contract(off)
 
@@ -29,8 +30,6 @@ namespace bsgp {
 
 namespace {
 
-__device__ __forceinline__ double ss_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
-__device__ __forceinline__ double ss_inf() { return __longlong_as_double(0x7ff0000000000000LL); }
 
 // imin = (int)ceil(pos - size / 2.0), kept inside +-kStampBoxLimit so that
 // imin + size is an int; a box clamped there has no overlap with any image
@@ -99,11 +98,11 @@ __global__ void __launch_bounds__(64) k_stamp_select(StampSelectArgs a) {
   const double flux_o = oc[0];
   // the running minimum from +inf of this lane's candidates, ascending: a
   // later equal score does not replace an earlier one, NaN replaces nothing
-  double low = ss_inf();
+  double low = dev_inf();
   int best = 0x7fffffff;
   for (int k = lane; k < a.K; k += 64) {
     const size_t i = (size_t)s * a.K + k;
-    double sc = ss_inf();
+    double sc = dev_inf();
     if (a.res_nlabels[i] > 0) sc = __dsub_rn(1.0, __ddiv_rn(a.res_cols[i * a.res_stride], flux_o));
     a.scores[i] = sc;
     if (sc < low) low = sc, best = k;
@@ -128,7 +127,7 @@ __global__ void __launch_bounds__(64) k_stamp_select(StampSelectArgs a) {
   row[0] = flux_o;
   row[5] = oc[3], row[6] = oc[4], row[7] = fwhm_o;
   if (st) {
-    const double q = ss_nan();
+    const double q = dev_nan();
     row[1] = q, row[2] = q, row[3] = q, row[4] = q, row[8] = q, row[9] = q, row[10] = q;
     a.num_iters[s] = -1;
   } else {

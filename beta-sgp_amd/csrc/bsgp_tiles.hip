@@ -15,7 +15,7 @@
 // table of the co-add.
 #include <hip/hip_runtime.h>
 
-#include "bsgp_internal.hpp"
+#include "bsgp_apps.hpp"
 
 namespace bsgp {
 

@@ -54,6 +54,40 @@ def test_ctypes_load_and_version():
     assert rc == -1 and b"storage" in L.bsgp_last_error()
 
 
+def header_arities():
+    """{function: number of parameters} of every declaration of include/bsgp.h:
+    the top-level commas of the text between its parentheses, `void` = none."""
+    txt = re.sub(r"/\*.*?\*/|//[^\n]*", " ", open(HEADER).read(), flags=re.S)
+    res = {}
+    for m in re.finditer(r"^\w[\w\s\*]*?\b(bsgp_\w+)\s*\(", txt, flags=re.M):
+        depth, commas, i = 1, 0, m.end()
+        while depth:
+            c = txt[i]
+            depth += (c == "(") - (c == ")")
+            commas += c == "," and depth == 1
+            i += 1
+        params = txt[m.end():i - 1].strip()
+        res[m.group(1)] = 0 if params in ("", "void") else commas + 1
+    return res
+
+
+def test_binding_arity_matches_header():
+    """A wrong arity in ctypes is silent until it corrupts a call: the binding's
+    one table lists every function the header declares, with as many argument
+    types as the declaration has parameters."""
+    import _bsgp
+    arity = header_arities()
+    assert sorted(arity) == header_functions()
+    assert arity["bsgp_device_synchronize"] == 0 and arity["bsgp_plan_destroy"] == 1
+    assert arity["bsgp_match_catalogs"] == 23
+    L = _bsgp.lib()
+    assert sorted(_bsgp.EXPORTED) == sorted(arity)
+    for name, n in arity.items():
+        argtypes = getattr(L, name).argtypes
+        assert argtypes is not None, name
+        assert len(argtypes) == n, (name, len(argtypes), n)
+
+
 def test_dropin_signatures_match_reference():
     import flux_conserve_proj as fcp
     import sgp
