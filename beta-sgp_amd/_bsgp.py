@@ -49,6 +49,7 @@ BSGP_STAMP_PARTIAL, BSGP_STAMP_NO_OVERLAP, BSGP_STAMP_BAD_POSITION = 1, 2, 4
 BSGP_STAMP_NO_SOURCE, BSGP_STAMP_MULTI_SOURCE, BSGP_STAMP_BAD_FLUX = 8, 16, 32
 BSGP_STAMP_NO_CANDIDATE, BSGP_STAMP_RESTORED_NO_SOURCE = 64, 128
 BSGP_STAMP_ROW_COLS = 11  # columns of a bsgp_stamp_select result row
+BSGP_VALIDATE_MAX = 16384  # values of one source-validation window in LDS (include/bsgp.h)
 # status bits of the background-matched co-add (include/bsgp.h)
 BSGP_COADD_NONFINITE, BSGP_COADD_ISOLATED, BSGP_COADD_NOT_CONVERGED = 1, 2, 4
 # bsgp_convolve2d_ex (include/bsgp.h): kernel size per axis, flags, status bits
@@ -198,6 +199,8 @@ _ENTRY_POINTS = {
     "bsgp_wasserstein1": [_P, _P, _P, _P, _i32, _i32, _P, _P],
     "bsgp_extract_stamps": [_P, _i32, _i32, _i32, _P, _i32, _i32, _i32, _P, _P, _P, _P],
     "bsgp_stamp_select": [_P, _P, _i32, _P, _i32, _P, _i32, _i32, _P, _P, _P, _P, _P, _P],
+    "bsgp_validate_sources": [_P, _i32, _P, _P, _i32, _i32, _i32, _i32, _P, _i32, _P, _i32, _i32,
+                              _i32, _dbl, _P, _P, _P, _P],
 }
 EXPORTED = list(_ENTRY_POINTS) + ["bsgp_last_error", "bsgp_abi_version"]
 

@@ -3,7 +3,7 @@
 // co-add, FITS pixels, PSF stamps,
 // sky background, convolution, detection, catalogue, local background,
 // deblending, catalogue cross-match, star-stamp metrics, cutouts and selection,
-// and the divergences.
+// source validation, and the divergences.
 // Each validates its arguments and launches its kernels.
 #include <cmath>
 #include <cstdio>
@@ -621,6 +621,45 @@ int bsgp_stamp_select(const int32_t* res_nlabels, const double* res_cols, int32_
   a.scores = scores_out, a.best = best_out, a.rows = rows_out, a.num_iters = num_iters_out;
   a.status = status_out;
   HIP_TRY(launch_stamp_select(a, (hipStream_t)stream));
+  return BSGP_OK;
+}
+
+int bsgp_validate_sources(const void* image, int32_t dtype, const double* bkgmap,
+                          const double* rmsmap, int32_t B, int32_t H, int32_t W,
+                          int32_t maps_per_image, const double* xy, int32_t xy_stride,
+                          const int32_t* n, int32_t cap, int32_t sh, int32_t sw, double nsigma,
+                          double* stats_out, int32_t* valid_out, int32_t* status_out,
+                          void* stream) {
+  if (B < 0 || cap < 0) return fail(BSGP_ERR_ARG, "B and cap must be >= 0");
+  if (int rc = check_dtype(dtype)) return rc;
+  if (H < 1 || W < 1) return fail(BSGP_ERR_ARG, "H and W must be >= 1");
+  if (sh < 1 || sw < 1) return fail(BSGP_ERR_ARG, "the window size (sh, sw) must be >= 1");
+  if (xy_stride < 2) return fail(BSGP_ERR_ARG, "xy_stride must be >= 2");
+  if (std::isnan(nsigma)) return fail(BSGP_ERR_ARG, "nsigma is NaN");
+  if ((int64_t)sh * sw > kValidateMax) {
+    char msg[128];
+    snprintf(msg, sizeof msg, "window of %lld values: a validation window holds at most %d",
+             (long long)sh * sw, kValidateMax);
+    return fail(BSGP_ERR_UNSUPPORTED, msg);
+  }
+  if (B == 0 || cap == 0) return BSGP_OK;
+  if (int rc = seg_shape(B, H, W)) return rc;
+  if (!image || !bkgmap || !rmsmap) return fail(BSGP_ERR_ARG, "image / bkgmap / rmsmap is NULL");
+  if (!xy) return fail(BSGP_ERR_ARG, "xy is NULL");
+  if (!stats_out || !valid_out || !status_out)
+    return fail(BSGP_ERR_ARG, "stats_out / valid_out / status_out is NULL");
+  ValidateArgs a{};
+  a.img = image, a.bkg = bkgmap, a.rms = rmsmap, a.xy = xy, a.n = n;
+  a.B = B, a.H = H, a.W = W, a.maps_per_image = maps_per_image ? 1 : 0, a.xy_stride = xy_stride;
+  a.cap = cap, a.sh = sh, a.sw = sw, a.nsigma = nsigma;
+  a.stats = stats_out, a.valid = valid_out, a.status = status_out;
+  hipStream_t s = (hipStream_t)stream;
+  const size_t rows = (size_t)B * cap;
+  // rows beyond an image's count: NaN statistics (all bits set), valid 0, status 0
+  HIP_TRY(hipMemsetAsync(stats_out, 0xff, 3 * rows * sizeof(double), s));
+  HIP_TRY(hipMemsetAsync(valid_out, 0, rows * sizeof(int), s));
+  HIP_TRY(hipMemsetAsync(status_out, 0, rows * sizeof(int), s));
+  HIP_TRY(launch_validate(a, dtype == BSGP_DTYPE_F32, s));
   return BSGP_OK;
 }
 

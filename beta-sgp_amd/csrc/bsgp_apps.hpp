@@ -1,7 +1,7 @@
 // bsgp_apps.hpp — the application stages' argument blocks, limits and launch
 // declarations: what their kernel units (bsgp_tiles, bsgp_coadd, bsgp_psf,
 // bsgp_background, bsgp_segment, bsgp_convolve, bsgp_localbkg, bsgp_match,
-// bsgp_deblend, bsgp_stamps, bsgp_starstamps .hip) share with the C-ABI host
+// bsgp_deblend, bsgp_stamps, bsgp_starstamps, bsgp_validate .hip) share with the C-ABI host
 // layer (bsgp_apps.hip).  Nothing of the solver.  Not part of the public interface.
 #pragma once
 
@@ -246,5 +246,20 @@ struct StampSelectArgs {
 };
 hipError_t launch_extract_stamps(const StampCutArgs& a, int f32, hipStream_t s);
 hipError_t launch_stamp_select(const StampSelectArgs& a, hipStream_t s);
+// ---- source validation (bsgp_validate.hip) -----------
+constexpr int kValidateMax = BSGP_VALIDATE_MAX;  // sh * sw of one window: 128 KiB of LDS
+struct ValidateArgs {
+  const void* img;              // [B][H][W] float32 or float64, not background-subtracted
+  const double *bkg, *rms;      // [H][W], or [B][H][W] when maps_per_image
+  const double* xy;             // (x, y) of row (b, r) at xy + (b * cap + r) * xy_stride
+  const int* n;                 // [B], or nullptr: cap
+  int B, H, W, maps_per_image, xy_stride, cap, sh, sw;
+  int P;                        // the power of two >= sh * sw (the sort's size; the launch fills it in)
+  double nsigma;
+  double* stats;  // [B][cap][3]: source_pixs, bkg, rms
+  int* valid;     // [B][cap]
+  int* status;    // [B][cap]: BSGP_STAMP_PARTIAL / NO_OVERLAP / BAD_POSITION
+};
+hipError_t launch_validate(ValidateArgs a, int f32, hipStream_t s);
 
 }  // namespace bsgp

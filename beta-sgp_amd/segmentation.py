@@ -545,7 +545,9 @@ class SourceCatalog:
     raises ``KeyError``; ``sky_centroid`` and ``segment_fluxerr`` always do,
     with the reason.  ``device_out=True`` adds ``int_cols`` / ``f64_cols`` (CUDA
     tensors [B, cap, 5] / [B, cap, 8]) and, with a width,
-    ``local_background_dev`` [B, cap]."""
+    ``local_background_dev`` [B, cap].  A catalogue made by
+    ``source_info(..., validate=True)`` also has the bool column ``valid``,
+    ``validation`` and ``segment_flux_sum_valid``."""
 
     def __init__(self, data, segment_img, convolved_data=None, background=None, device_out=False,
                  localbkg_width=0):
@@ -574,7 +576,10 @@ class SourceCatalog:
         self._fill(d, c, lab, n, batched, device_out, width)
         self.background = background
 
-    def _fill(self, d, c, lab, n, batched, device_out, localbkg_width=0.0):
+    def _fill(self, d, c, lab, n, batched, device_out, localbkg_width=0.0, validate=None):
+        """validate: None, or (image, bkgmap, rmsmap, (ny, nx)) on the device --
+        the unsubtracted image and its maps: the rows are validated from their
+        centroid columns in place."""
         torch = _B.torch
         B, H, W = d.shape
         cap = max(1, int(n.max()))
@@ -595,6 +600,11 @@ class SourceCatalog:
                 _B._ptr(fc), float(localbkg_width), LOCALBKG_SIGMA, LOCALBKG_MAXITERS,
                 LOCALBKG_MIN_PIXELS, 1, _B._ptr(lbd), _B._ptr(npx), _B._ptr(lst),
                 _B.current_stream()))
+        val = None
+        if validate is not None:  # V1 to V6 from the centroid columns (stream-ordered, no copy)
+            img, bg, rms, (vh, vw) = validate
+            val = _validate_dev(img, bg, rms, ctypes.c_void_p(fc.data_ptr() + 3 * 8), 8, nd, cap,
+                                vh, vw, 3.0)
         ich, fch, sth = ic.cpu().numpy(), fc.cpu().numpy(), st.cpu().numpy()
         if sth.any():
             raise _B.BsgpError(_B.BSGP_ERR_ARG, f"image {int(np.flatnonzero(sth)[0])}: labels "
@@ -628,6 +638,17 @@ class SourceCatalog:
         # one fixed order for the total as well: numpy's sum of the per-segment fluxes
         tot = np.array([float(np.sum(v)) for v in cols["segment_flux"]])
         self.segment_flux_sum = tot if batched else float(tot[0])
+        if val is not None:
+            stats, valid, status = val
+            self.validation = SourceValidation(valid.cpu().numpy(), stats.cpu().numpy(),
+                                               status.cpu().numpy(), n, batched)
+            if device_out:
+                self.validation.valid_dev, self.validation.stats_dev = valid, stats
+                self.validation.status_dev = status
+            ok = self.validation.valid if batched else [self.validation.valid]
+            cols["valid"] = list(ok)
+            tot = np.array([float(np.sum(f[v])) for f, v in zip(cols["segment_flux"], ok)])
+            self.segment_flux_sum_valid = tot if batched else float(tot[0])
 
     def __getattr__(self, name):
         if name.startswith("_"):
@@ -651,12 +672,13 @@ class SourceCatalog:
     def to_dict(self, columns=None):
         """The named columns (default: all) as a dict; unknown and unavailable
         names raise ``KeyError``."""
-        every = COLUMNS + (("local_background",) if "local_background" in self._cols else ())
+        every = COLUMNS + tuple(k for k in ("local_background", "valid") if k in self._cols)
         return {k: self[k] for k in (every if columns is None else columns)}
 
 
 def source_info(data, box_size, n_pixels=5, sigma_threshold=1.5, device_out=False, deblend=False,
-                nlevels=32, contrast=0.001, large_parents=False, localbkg_width=0):
+                nlevels=32, contrast=0.001, large_parents=False, validate=False, validate_size=100,
+                localbkg_width=0):
     """``utils.source_info`` (restoration/utils.py:235-247) for an image or a
     batch, with its deblending on request: ``Background2D(data, box_size,
     filter_size=(3, 3))``, ``sub = data - background``, ``threshold =
@@ -676,10 +698,25 @@ def source_info(data, box_size, n_pixels=5, sigma_threshold=1.5, device_out=Fals
     Returns ``(catalog, bkg)``; the catalogue also carries ``segment_img``,
     ``data`` (sub) and ``convolved_data``.  An unbatched image without a
     detection warns and gives ``(None, bkg)``.  With ``device_out=True`` the
-    maps stay on the device."""
+    maps stay on the device.
+
+    ``validate=True`` runs the reference's ``validation_source``
+    (utils.py:313-329; :func:`validate_sources`) on every row,
+    at its centroid, with the unsubtracted ``data``, ``bkg.background`` and
+    ``bkg.background_rms`` as they are on the device and windows of
+    ``validate_size``: the catalogue gains the bool column ``valid``, the
+    attribute ``validation`` (a :class:`SourceValidation`) and
+    ``segment_flux_sum_valid``, numpy's sum of ``segment_flux`` over the valid
+    rows.  No row is dropped: the labels stay those of ``segment_img``.  A row
+    with a NaN centroid is invalid (``BSGP_STAMP_BAD_POSITION``).  The default
+    ``False`` leaves every output as it is without the parameter."""
     from background import Background2D
     torch = _B.torch
     _check_image_shape(_shape_of(data))
+    vsize = None
+    if validate:
+        shp = _shape_of(data)
+        vsize = check_validate_args(shp, shp, shp, validate_size)
     check_detect_args(_shape_of(data), n_pixels, 8)
     check_deblend_args(_shape_of(data), _shape_of(data), n_pixels, nlevels, contrast,
                        large_parents=large_parents)
@@ -706,7 +743,8 @@ def source_info(data, box_size, n_pixels=5, sigma_threshold=1.5, device_out=Fals
                            large_parents=bool(large_parents))
         seg, (lab, n) = _deblended_image(res, batched, device_out), res[:2]
     cat = SourceCatalog.__new__(SourceCatalog)
-    cat._fill(sub, conv, lab, n.astype(np.int32), batched, device_out, width)
+    cat._fill(sub, conv, lab, n.astype(np.int32), batched, device_out, width,
+              validate=(d, bg, rms, vsize) if validate else None)
     cat.background = None
     cat.segment_img = seg or SegmentationImage(_out(lab, batched, device_out), n, batched)
     cat.data, cat.convolved_data = _out(sub, batched, device_out), _out(conv, batched, device_out)
@@ -774,6 +812,186 @@ def catalog_flux_fraction_score(gn, box_size=60, n_pixels_orig=5, n_pixels_resto
 
     score.batch = batch
     return score
+
+
+# ---- validation of detected sources (bsgp_validate_sources) ----
+VALIDATE_MAX = _B.BSGP_VALIDATE_MAX
+
+
+def _is_number(v):
+    return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_))
+
+
+def check_validate_args(image_shape, bkgmap_shape, rmsmap_shape, size=100, nsigma=3.0,
+                        positions_shape=None):
+    """The argument checks of validate_sources (host only; nothing touches the
+    GPU): the image is [H, W] or [B, H, W]; both maps have one shape, [H, W]
+    or (for a batch) [B, H, W]; ``size`` is a positive int or a pair (ny, nx)
+    of them with ``ny * nx <= VALIDATE_MAX``; ``nsigma`` is a number, not NaN;
+    ``positions_shape`` (when given) is the shape [n, 2] of the positions of an
+    image, or for a batch a list of B such shapes.  Returns (ny, nx)."""
+    shape = tuple(image_shape)
+    _check_image_shape(shape, "image")
+    for nm, s in (("bkgmap", tuple(bkgmap_shape)), ("rmsmap", tuple(rmsmap_shape))):
+        if s != shape[-2:] and not (len(shape) == 3 and s == shape):
+            raise ValueError(f"{nm} shape {s} does not match image shape {shape}: the maps are "
+                             "[H, W] or, for a batch, [B, H, W]")
+    if tuple(bkgmap_shape) != tuple(rmsmap_shape):
+        raise ValueError(f"bkgmap shape {tuple(bkgmap_shape)} and rmsmap shape "
+                         f"{tuple(rmsmap_shape)} differ")
+    sz = (size, size) if np.ndim(size) == 0 else tuple(np.asarray(size).tolist())
+    if len(sz) != 2 or not all(_is_number(v) and int(v) == v and v >= 1 for v in sz):
+        raise ValueError(f"size must be an int >= 1 or a pair (ny, nx) of them, got {size!r}")
+    sh, sw = int(sz[0]), int(sz[1])
+    if sh * sw > VALIDATE_MAX:
+        raise ValueError(f"size {size!r}: a window of {sh * sw} values, the device holds at most "
+                         f"VALIDATE_MAX = {VALIDATE_MAX} (128 x 128)")
+    if not _is_number(nsigma) or np.isnan(nsigma):
+        raise ValueError(f"nsigma must be a number, got {nsigma!r}")
+    if positions_shape is not None:
+        if len(shape) == 3:
+            if not isinstance(positions_shape, list) or len(positions_shape) != shape[0]:
+                raise ValueError(f"a batch of {shape[0]} images needs a list of {shape[0]} position "
+                                 "arrays")
+            shapes = positions_shape
+        else:
+            if isinstance(positions_shape, list):
+                raise ValueError("a list of positions needs a batch of images [B, H, W]")
+            shapes = [positions_shape]
+        for s in shapes:
+            if len(tuple(s)) != 2 or tuple(s)[1] != 2:
+                raise ValueError(f"positions must be [n, 2] in (x, y), got shape {tuple(s)}")
+    return sh, sw
+
+
+class SourceValidation:
+    """Result of :func:`validate_sources`, one entry per source: ``valid``
+    (bool: ``source_pixs > bkg + nsigma * rms``), ``source_pixs`` (the mean of
+    the window's three largest image values), ``bkg`` (the median of the
+    background window), ``rms`` (the mean of the rms window) and ``status``
+    (``BSGP_STAMP_PARTIAL`` where the window leaves the frame;
+    ``BSGP_STAMP_NO_OVERLAP`` / ``BSGP_STAMP_BAD_POSITION``: invalid, NaN
+    statistics).  For a batch every attribute is a list over the images.  With
+    ``device_out=True`` the entries are CUDA tensors (views of ``valid_dev``
+    [B, cap] int32, ``stats_dev`` [B, cap, 3] and ``status_dev`` [B, cap])."""
+
+    def __init__(self, valid, stats, status, n, batched):
+        cols = dict(valid=[], source_pixs=[], bkg=[], rms=[], status=[])
+        for b, k in enumerate(n):
+            cols["valid"].append(valid[b, :k] != 0)
+            cols["source_pixs"].append(stats[b, :k, 0])
+            cols["bkg"].append(stats[b, :k, 1])
+            cols["rms"].append(stats[b, :k, 2])
+            cols["status"].append(status[b, :k])
+        self.batched = batched
+        for k, v in cols.items():
+            setattr(self, k, v if batched else v[0])
+
+
+def _validate_dev(d, bg, rms, xy, xy_stride, nd, cap, sh, sw, nsigma):
+    """(stats [B, cap, 3], valid [B, cap], status [B, cap]) CUDA tensors of
+    bsgp_validate_sources; asynchronous.  d: CUDA [B, H, W]; bg, rms: float64
+    CUDA [H, W] or [B, H, W]; xy: the pointer of the first (x, y); nd: int32
+    CUDA [B]."""
+    torch = _B.torch
+    B, H, W = d.shape
+    stats = torch.empty((B, cap, 3), dtype=torch.float64, device="cuda")
+    valid = torch.empty((B, cap), dtype=torch.int32, device="cuda")
+    status = torch.empty((B, cap), dtype=torch.int32, device="cuda")
+    _B.check(_B.lib().bsgp_validate_sources(
+        _B._ptr(d), _dtype(d), _B._ptr(bg), _B._ptr(rms), B, H, W, int(bg.dim() == 3), xy,
+        int(xy_stride), _B._ptr(nd), int(cap), int(sh), int(sw), float(nsigma), _B._ptr(stats),
+        _B._ptr(valid), _B._ptr(status), _B.current_stream()))
+    return stats, valid, status
+
+
+def _positions_of(p):
+    """[n, 2] float64 host array of one image's positions: an array in (x, y),
+    or anything with ``xcentroid`` / ``ycentroid`` columns."""
+    if isinstance(p, SourceCatalog) or isinstance(p, dict) or hasattr(p, "keys"):
+        if getattr(p, "batched", False):
+            raise ValueError("a batch is a list of unbatched catalogues")
+        x, y = _column(p, "xcentroid"), _column(p, "ycentroid")
+        if x is None or y is None:
+            raise ValueError("a catalogue needs the columns 'xcentroid' and 'ycentroid'")
+        return np.stack([x.astype(np.float64).reshape(-1), y.astype(np.float64).reshape(-1)], axis=1)
+    a = np.asarray(p, dtype=np.float64)
+    return a.reshape(0, 2) if a.size == 0 and a.ndim < 2 else a
+
+
+def validate_sources(image, positions, bkgmap, rmsmap, size=100, nsigma=3.0, device_out=False):
+    """The reference's ``utils.validation_source`` (restoration/utils.py:313-329)
+    for every source of an image or of a batch, on the device
+    (``bsgp_validate_sources``): a source is valid when
+    the mean of the three largest pixels of the ``size`` window around it
+    exceeds the window's median background by ``nsigma`` times its mean rms.
+
+    ``image`` ([H, W] or [B, H, W], float32 or float64) must not be
+    background-subtracted.  ``positions``: an array [n, 2] in (x, y), a
+    :class:`SourceCatalog` (its ``xcentroid`` / ``ycentroid``; one made with
+    ``device_out=True`` is read from its device columns, nothing is copied),
+    or for a batch a list of B arrays or unbatched catalogues, or a batched
+    :class:`SourceCatalog`.  ``bkgmap`` / ``rmsmap``: [H, W] for all images or
+    [B, H, W]; they are widened to float64.  ``size``: an int or (ny, nx), at
+    most ``VALIDATE_MAX`` cells.  The window is ``Cutout2D``'s in mode
+    'partial' with ``fill_value=0.0``: cells outside the frame are 0.0 and take
+    part in the statistics, as in the reference.  A position whose window
+    misses the frame, or that is not finite, is invalid with NaN statistics and
+    a status bit (astropy raises).  Returns a :class:`SourceValidation`."""
+    torch = _B.torch
+    shape = _shape_of(image)
+    _check_image_shape(shape, "image")
+    in_place = isinstance(positions, SourceCatalog) and hasattr(positions, "f64_cols")
+    if in_place:
+        if positions.batched != (len(shape) == 3) or \
+                (positions.batched and len(positions.nlabels) != shape[0]):
+            raise ValueError("the catalogue and the image differ in their batch")
+        sh, sw = check_validate_args(shape, _shape_of(bkgmap), _shape_of(rmsmap), size, nsigma)
+        n = np.atleast_1d(np.asarray(positions.nlabels, dtype=np.int32))
+    else:
+        if isinstance(positions, SourceCatalog) and positions.batched:
+            positions = [{"xcentroid": x, "ycentroid": y}
+                         for x, y in zip(positions["xcentroid"], positions["ycentroid"])]
+        # a list is a batch only beside a batch of images: [[x, y], ...] is one image's array
+        pos = [_positions_of(p) for p in positions] \
+            if isinstance(positions, list) and len(shape) == 3 else _positions_of(positions)
+        sh, sw = check_validate_args(shape, _shape_of(bkgmap), _shape_of(rmsmap), size, nsigma,
+                                     [p.shape for p in pos] if isinstance(pos, list) else pos.shape)
+        pos = pos if isinstance(pos, list) else [pos]
+        n = np.array([len(p) for p in pos], dtype=np.int32)
+    _B.require_gpu()
+    d, batched = _to_dev(image)
+    bg, rm = (_to_dev(m, keep_f32=False)[0] for m in (bkgmap, rmsmap))
+    if len(_shape_of(bkgmap)) == 2:
+        bg, rm = bg[0], rm[0]
+    if in_place:
+        fc = positions.f64_cols
+        cap, xy, stride = int(fc.shape[1]), ctypes.c_void_p(fc.data_ptr() + 3 * 8), 8
+        keep = fc
+    else:
+        cap = max(1, int(n.max()))
+        host = np.zeros((len(pos), cap, 2))
+        for b, p in enumerate(pos):
+            host[b, :len(p)] = p
+        keep = torch.from_numpy(host).to("cuda")
+        xy, stride = _B._ptr(keep), 2
+    nd = torch.from_numpy(np.ascontiguousarray(n)).to("cuda")
+    stats, valid, status = _validate_dev(d, bg, rm, xy, stride, nd, cap, sh, sw, nsigma)
+    if device_out:
+        out = SourceValidation(valid, stats, status, n, batched)
+        out.valid_dev, out.stats_dev, out.status_dev = valid, stats, status
+        out._keep = (d, bg, rm, keep, nd)
+        return out
+    vh, sth, sh_ = valid.cpu().numpy(), stats.cpu().numpy(), status.cpu().numpy()  # waits
+    return SourceValidation(vh, sth, sh_, n, batched)
+
+
+def validation_source(image, coord, bkgmap, rmsmap, size=100):
+    """``utils.validation_source(image, coord, bkgmap, rmsmap, size=100)``
+    (restoration/utils.py:313-329) for one source at ``coord = (x, y)``: a
+    Python ``bool``, the ``valid`` of the one-row :func:`validate_sources`."""
+    pos = np.asarray(coord, dtype=np.float64).reshape(1, 2)
+    return bool(validate_sources(image, pos, bkgmap, rmsmap, size=size).valid[0])
 
 
 # ---- cross-match of two catalogues (bsgp_match_catalogs; DESIGN §3.10, M1 to M6) ----

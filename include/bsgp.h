@@ -815,6 +815,54 @@ int bsgp_stamp_select(const int32_t* res_nlabels, const double* res_cols, int32_
                       int32_t K, double* scores_out, int32_t* best_out, double* rows_out,
                       int32_t* num_iters_out, int32_t* status_out, void* stream);
 
+/* Validation of detected sources: the reference's
+ * utils.validation_source(image, coord, bkgmap, rmsmap, size)
+ * (restoration/utils.py:313-329) for up to cap sources in each of B images, in
+ * one launch.  Asynchronous; B == 0 or cap == 0 is a no-op that follows no
+ * pointer.
+ *   image   device [B][H][W], float32 or float64 (dtype = BSGP_DTYPE_*), NOT
+ *           background-subtracted
+ *   bkgmap, rmsmap   device float64 [H][W] shared by all images
+ *           (maps_per_image == 0) or [B][H][W] (maps_per_image != 0)
+ *   xy      device float64: (x, y) = (column, row) of source r of image b at
+ *           xy + (b * cap + r) * xy_stride, xy_stride >= 2 (2: a packed
+ *           [B][cap][2]; 8 with xy = f64_cols + 3: the centroid columns of
+ *           bsgp_segment_catalog, read in place)
+ *   n       device int32 [B]: sources of image b (rows beyond min(n, cap) are
+ *           not read), or NULL: cap
+ * Per source the window is the box of Cutout2D(., (x, y), (sh, sw),
+ * mode='partial', fill_value=0.0): per axis it starts at (int)ceil(pos -
+ * size / 2.0) (astropy 4.3.1, as bsgp_extract_stamps) and has size cells;
+ * cells outside the frame hold 0.0 and take part in every statistic.  With
+ * the N = sh * sw values of each window:
+ *   stats_out [B][cap][3] = source_pixs, bkg, rms
+ *     source_pixs  the mean of the min(3, N) largest image values, summed in
+ *                  ascending order and divided in the image's own type (each
+ *                  operation rounded to float32 for a float32 image), as
+ *                  np.sort(c.flatten())[-3:].mean(); then widened
+ *     bkg          np.median of the bkgmap values: the middle one, or (a + b) / 2
+ *                  of the two middle ones
+ *     rms          numpy's pairwise sum of the rmsmap values in raster order,
+ *                  divided by N
+ *   valid_out [B][cap]  = source_pixs > bkg + nsigma * rms (float64, strict;
+ *                  the reference's nsigma is 3); 0 when a term is NaN
+ *   status_out [B][cap] = 0 or BSGP_STAMP_PARTIAL (informational: the box
+ *                  leaves the frame), BSGP_STAMP_NO_OVERLAP, BSGP_STAMP_BAD_POSITION
+ *                  (astropy raises for both: valid = 0 and the three
+ *                  statistics are NaN)
+ * A NaN in a window makes that window's statistic NaN; +-inf follow IEEE.
+ * Rows beyond an image's count keep valid 0, status 0 and NaN statistics.
+ * BSGP_ERR_ARG: a NULL array, an unknown dtype, B, cap < 0, H, W, sh or sw < 1,
+ * xy_stride < 2, a NaN nsigma; BSGP_ERR_UNSUPPORTED: sh * sw > BSGP_VALIDATE_MAX
+ * (the window is held in 128 KiB of LDS), H * W >= 2^31, B > 65535. */
+#define BSGP_VALIDATE_MAX 16384
+int bsgp_validate_sources(const void* image, int32_t dtype, const double* bkgmap,
+                          const double* rmsmap, int32_t B, int32_t H, int32_t W,
+                          int32_t maps_per_image, const double* xy, int32_t xy_stride,
+                          const int32_t* n, int32_t cap, int32_t sh, int32_t sw, double nsigma,
+                          double* stats_out, int32_t* valid_out, int32_t* status_out,
+                          void* stream);
+
 int bsgp_device_synchronize(void);
 const char* bsgp_last_error(void);
 /* The persistent solver's compile-time-geometry path (256 x 256 images on a
