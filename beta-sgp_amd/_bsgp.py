@@ -50,6 +50,11 @@ BSGP_STAMP_NO_SOURCE, BSGP_STAMP_MULTI_SOURCE, BSGP_STAMP_BAD_FLUX = 8, 16, 32
 BSGP_STAMP_NO_CANDIDATE, BSGP_STAMP_RESTORED_NO_SOURCE = 64, 128
 BSGP_STAMP_ROW_COLS = 11  # columns of a bsgp_stamp_select result row
 BSGP_VALIDATE_MAX = 16384  # values of one source-validation window in LDS (include/bsgp.h)
+# the PSF fit (include/bsgp.h): limits, per-star status bits, the frame's
+BSGP_PSFFIT_MAX_COEF, BSGP_PSFFIT_MAX_STARS = 108, 4096
+BSGP_PSFFIT_PARTIAL, BSGP_PSFFIT_BAD_POSITION, BSGP_PSFFIT_NO_OVERLAP = 1, 2, 4
+BSGP_PSFFIT_FEW_PIXELS, BSGP_PSFFIT_BAD_FLUX, BSGP_PSFFIT_BAD_WEIGHT = 8, 16, 32
+BSGP_PSFFIT_CLIPPED, BSGP_PSFFIT_EXCLUDED, BSGP_PSFFIT_SINGULAR = 64, 2 | 4 | 8 | 16 | 32, 128
 # status bits of the background-matched co-add (include/bsgp.h)
 BSGP_COADD_NONFINITE, BSGP_COADD_ISOLATED, BSGP_COADD_NOT_CONVERGED = 1, 2, 4
 # bsgp_convolve2d_ex (include/bsgp.h): kernel size per axis, flags, status bits
@@ -201,6 +206,10 @@ _ENTRY_POINTS = {
     "bsgp_stamp_select": [_P, _P, _i32, _P, _i32, _P, _i32, _i32, _P, _P, _P, _P, _P, _P],
     "bsgp_validate_sources": [_P, _i32, _P, _P, _i32, _i32, _i32, _i32, _P, _i32, _P, _i32, _i32,
                               _i32, _dbl, _P, _P, _P, _P],
+    "bsgp_psf_fit_moments": [_P, _i32, _i32, _i32, _i32, _P, _P, _i32, ctypes.POINTER(PsfModel),
+                             _dbl, _P, _P, _i32, _P, _i32, _dbl, _P, _P, _P, _P, _P, _P, _P],
+    "bsgp_psf_fit_solve": [_i32, _i32, _P, _P, ctypes.POINTER(PsfModel), _P, _P, _P, _P, _P, _P,
+                           _i32, _dbl, _i32, _P, _P, _P, _P, _P, _P],
 }
 EXPORTED = list(_ENTRY_POINTS) + ["bsgp_last_error", "bsgp_abi_version"]
 

@@ -3,7 +3,7 @@
 // co-add, FITS pixels, PSF stamps,
 // sky background, convolution, detection, catalogue, local background,
 // deblending, catalogue cross-match, star-stamp metrics, cutouts and selection,
-// source validation, and the divergences.
+// source validation, the PSF fit, and the divergences.
 // Each validates its arguments and launches its kernels.
 #include <cmath>
 #include <cstdio>
@@ -660,6 +660,102 @@ int bsgp_validate_sources(const void* image, int32_t dtype, const double* bkgmap
   HIP_TRY(hipMemsetAsync(valid_out, 0, rows * sizeof(int), s));
   HIP_TRY(hipMemsetAsync(status_out, 0, rows * sizeof(int), s));
   HIP_TRY(launch_validate(a, dtype == BSGP_DTYPE_F32, s));
+  return BSGP_OK;
+}
+
+namespace {
+// the shape header of a fit from the caller's model, its sizes checked
+int psffit_shape(const bsgp_psf_model* m, int32_t B, int32_t cap, PsfShape* out) {
+  if (B < 0 || cap < 0) return fail(BSGP_ERR_ARG, "B and cap must be >= 0");
+  if (!m) return fail(BSGP_ERR_ARG, "model is NULL");
+  if (m->hw < 0 || m->hw > 255 || m->ngauss < 1 || m->ldeg < 0 || m->sdeg < 0)
+    return fail(BSGP_ERR_ARG, "bad PSF model degrees or half width");
+  const int64_t ncomp = (int64_t)m->ngauss * (m->ldeg + 1) * (m->ldeg + 2) / 2;
+  const int64_t nterm = (int64_t)(m->sdeg + 1) * (m->sdeg + 2) / 2;
+  if (m->ngauss > kPsfFitMaxCoef || m->ldeg > kPsfFitMaxCoef || m->sdeg > kPsfFitMaxCoef ||
+      ncomp * nterm > kPsfFitMaxCoef) {
+    char msg[128];
+    snprintf(msg, sizeof msg, "a model of %lld coefficients: a fit holds at most %d",
+             (long long)(ncomp * nterm), kPsfFitMaxCoef);
+    return fail(BSGP_ERR_UNSUPPORTED, msg);
+  }
+  if (cap > kPsfFitMaxStars) {
+    char msg[128];
+    snprintf(msg, sizeof msg, "%d stars: a frame holds at most %d", cap, kPsfFitMaxStars);
+    return fail(BSGP_ERR_UNSUPPORTED, msg);
+  }
+  if (B > 65535) return fail(BSGP_ERR_UNSUPPORTED, "B must be at most 65535");
+  PsfShape s{};
+  s.cosv = m->cos, s.sinv = m->sin, s.ax = m->ax, s.ay = m->ay;
+  s.sig2 = m->sigma_inc * m->sigma_inc;
+  s.x_orig = m->x_orig, s.y_orig = m->y_orig;
+  s.ngauss = m->ngauss, s.ldeg = m->ldeg, s.sdeg = m->sdeg, s.hw = m->hw;
+  s.ncomp = (int)ncomp, s.nterm = (int)nterm;
+  *out = s;
+  return BSGP_OK;
+}
+}  // namespace
+
+int bsgp_psf_fit_moments(const void* image, int32_t dtype, int32_t B, int32_t H, int32_t W,
+                         const double* xy, const int32_t* n, int32_t cap,
+                         const bsgp_psf_model* model, double fitrad, const double* flux,
+                         const double* sky, int32_t sky_mode, const uint8_t* mask, int32_t has_sat,
+                         double sat_level, double* G_out, double* h_out, double* vv_out,
+                         int32_t* npix_out, double* flux_out, int32_t* status_out, void* stream) {
+  PsfFitMomentArgs a{};
+  if (int rc = psffit_shape(model, B, cap, &a.shape)) return rc;
+  if (int rc = check_dtype(dtype)) return rc;
+  if (H < 1 || W < 1) return fail(BSGP_ERR_ARG, "H and W must be >= 1");
+  if (!(fitrad > 0.0)) return fail(BSGP_ERR_ARG, "fitrad must be > 0");
+  if (sky_mode < 0 || sky_mode > 2) return fail(BSGP_ERR_ARG, "sky_mode must be 0, 1 or 2");
+  if (B == 0 || cap == 0) return BSGP_OK;
+  if (int rc = seg_shape(B, H, W)) return rc;
+  if (!image || !xy) return fail(BSGP_ERR_ARG, "image / xy is NULL");
+  if (sky_mode != 0 && !sky) return fail(BSGP_ERR_ARG, "sky is NULL");
+  if (!G_out || !h_out || !vv_out || !npix_out || !flux_out || !status_out)
+    return fail(BSGP_ERR_ARG, "G_out / h_out / vv_out / npix_out / flux_out / status_out is NULL");
+  a.img = image, a.xy = xy, a.n = n, a.flux = flux, a.sky = sky_mode ? sky : nullptr, a.mask = mask;
+  a.B = B, a.H = H, a.W = W, a.cap = cap, a.sky_mode = sky_mode, a.has_sat = has_sat ? 1 : 0;
+  a.fitrad2 = fitrad * fitrad, a.sat_level = sat_level;
+  a.G = G_out, a.h = h_out, a.vv = vv_out, a.flux_out = flux_out, a.npix = npix_out;
+  a.status = status_out;
+  hipStream_t s = (hipStream_t)stream;
+  const size_t rows = (size_t)B * cap, nc = a.shape.ncomp;
+  HIP_TRY(hipMemsetAsync(G_out, 0, rows * (nc * (nc + 1) / 2) * sizeof(double), s));
+  HIP_TRY(hipMemsetAsync(h_out, 0, rows * nc * sizeof(double), s));
+  HIP_TRY(hipMemsetAsync(vv_out, 0, rows * sizeof(double), s));
+  HIP_TRY(hipMemsetAsync(flux_out, 0, rows * sizeof(double), s));
+  HIP_TRY(hipMemsetAsync(npix_out, 0, rows * sizeof(int), s));
+  HIP_TRY(hipMemsetAsync(status_out, 0, rows * sizeof(int), s));
+  HIP_TRY(launch_psffit_moments(a, dtype == BSGP_DTYPE_F32, s));
+  return BSGP_OK;
+}
+
+int bsgp_psf_fit_solve(int32_t B, int32_t cap, const int32_t* n, const double* xy,
+                       const bsgp_psf_model* model, const double* G, const double* h,
+                       const double* vv, const int32_t* npix, const int32_t* mstatus,
+                       const double* weights, int32_t niter, double nsig, int32_t min_stars,
+                       double* coef_out, int32_t* used_out, int32_t* status_out, double* rms_out,
+                       int32_t* frame_out, void* stream) {
+  PsfFitSolveArgs a{};
+  if (int rc = psffit_shape(model, B, cap, &a.shape)) return rc;
+  if (niter < 0 || min_stars < 0) return fail(BSGP_ERR_ARG, "niter and min_stars must be >= 0");
+  if (std::isnan(nsig)) return fail(BSGP_ERR_ARG, "nsig is NaN");
+  if (B == 0 || cap == 0) return BSGP_OK;
+  if (!xy || !G || !h || !vv || !npix || !mstatus)
+    return fail(BSGP_ERR_ARG, "xy / G / h / vv / npix / mstatus is NULL");
+  if (!coef_out || !used_out || !status_out || !rms_out || !frame_out)
+    return fail(BSGP_ERR_ARG, "coef_out / used_out / status_out / rms_out / frame_out is NULL");
+  a.xy = xy, a.n = n, a.G = G, a.h = h, a.vv = vv, a.npix = npix, a.mstatus = mstatus;
+  a.weights = weights;
+  a.B = B, a.cap = cap, a.niter = niter, a.min_stars = min_stars, a.nsig = nsig;
+  a.coef = coef_out, a.rms = rms_out, a.used = used_out, a.status = status_out;
+  a.frame = frame_out;
+  hipStream_t s = (hipStream_t)stream;
+  // rows beyond a frame's count: status 0, rms NaN (all bits set)
+  HIP_TRY(hipMemsetAsync(status_out, 0, (size_t)B * cap * sizeof(int), s));
+  HIP_TRY(hipMemsetAsync(rms_out, 0xff, (size_t)B * cap * sizeof(double), s));
+  HIP_TRY(launch_psffit_solve(a, s));
   return BSGP_OK;
 }
 

@@ -1,13 +1,14 @@
 // bsgp_apps.hpp — the application stages' argument blocks, limits and launch
 // declarations: what their kernel units (bsgp_tiles, bsgp_coadd, bsgp_psf,
 // bsgp_background, bsgp_segment, bsgp_convolve, bsgp_localbkg, bsgp_match,
-// bsgp_deblend, bsgp_stamps, bsgp_starstamps, bsgp_validate .hip) share with the C-ABI host
+// bsgp_deblend, bsgp_stamps, bsgp_starstamps, bsgp_validate, bsgp_psffit .hip) share with the C-ABI host
 // layer (bsgp_apps.hip).  Nothing of the solver.  Not part of the public interface.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include "../../include/bsgp.h"
+#include "bsgp_psffit.hpp"  // PsfShape
 
 namespace bsgp {
 
@@ -261,5 +262,41 @@ struct ValidateArgs {
   int* status;    // [B][cap]: BSGP_STAMP_PARTIAL / NO_OVERLAP / BAD_POSITION
 };
 hipError_t launch_validate(ValidateArgs a, int f32, hipStream_t s);
+// ---- PSF fit (bsgp_psffit.hip) -----------------------
+constexpr int kPsfFitMaxCoef = BSGP_PSFFIT_MAX_COEF;    // P: the packed normal matrix is 46 KiB of LDS
+constexpr int kPsfFitMaxStars = BSGP_PSFFIT_MAX_STARS;  // per frame: their rms is sorted in 32 KiB
+struct PsfFitMomentArgs {
+  const void* img;            // [B][H][W] float32 or float64
+  const double* xy;           // [B][cap][2]: (x, y) = (column, row)
+  const int* n;               // [B], or nullptr: cap
+  const double* flux;         // [B][cap], or nullptr: the sum of I - sky over the fit pixels
+  const double* sky;          // sky_mode 0: none; 1: [B][cap] per star; 2: [B][H][W] maps
+  const unsigned char* mask;  // [B][H][W] bytes, nonzero = skipped, or nullptr
+  PsfShape shape;
+  int B, H, W, cap, sky_mode, has_sat;
+  int chunk;  // candidates per round of the box walk (the launch fills it in)
+  double fitrad2, sat_level;
+  double *G, *h, *vv;  // [B][cap][ncomp (ncomp + 1) / 2], [B][cap][ncomp], [B][cap] (zeroed first)
+  double* flux_out;    // [B][cap]
+  int *npix, *status;  // [B][cap] (zeroed first)
+};
+struct PsfFitSolveArgs {
+  const double* xy;       // [B][cap][2]
+  const int* n;           // [B], or nullptr: cap
+  const double *G, *h, *vv;
+  const int *npix, *mstatus;  // as the moments wrote them
+  const double* weights;      // [B][cap], or nullptr: 1
+  PsfShape shape;
+  int B, cap, niter, min_stars;
+  int sortP;  // the power of two >= cap (the launch fills it in)
+  double nsig;
+  double* coef;        // [B][P]
+  double* rms;         // [B][cap]
+  int *used, *status;  // [B][cap]
+  int* frame;          // [B][3]: status, rounds, stars used
+};
+int psffit_chunk(int ncomp);
+hipError_t launch_psffit_moments(PsfFitMomentArgs a, int f32, hipStream_t s);
+hipError_t launch_psffit_solve(PsfFitSolveArgs a, hipStream_t s);
 
 }  // namespace bsgp

@@ -32,40 +32,60 @@ struct PsfModel {
   double coef[kPsfMaxCoef];
 };
 
+// The spatial terms of init_psf (:154-165) in its loop order: f(term, a1, a2)
+// with a1 = dx^m and a2 = dy^n as its running products form them.  Evaluation
+// (psf_local_coef) and fitting (bsgp_psffit.hpp) both go through here.
+template <class F>
+BSGP_HD void psf_spatial_terms(int sdeg, double dx, double dy, F&& f) {
+  int term = 0;
+  double a1 = 1.0;
+  for (int m = 0; m <= sdeg; ++m) {
+    double a2 = 1.0;
+    for (int n = 0; n <= sdeg - m; ++n) {
+      f(term, a1, a2);
+      ++term;
+      a2 *= dy;
+    }
+    a1 *= dx;
+  }
+}
+
+// Local coefficient icomp at field offset (dx, dy) from the expansion origin:
+// sum over spatial terms of coef[term * ncomp + icomp] * dx^m * dy^n.
+BSGP_HD double psf_local_coef_at(const double* coef, int ncomp, int sdeg, int icomp, double dx,
+                                 double dy) {
+  double v = 0.0;
+  psf_spatial_terms(sdeg, dx, dy, [&](int term, double a1, double a2) {
+    v += coef[term * ncomp + icomp] * a1 * a2;
+  });
+  return v;
+}
+
 // Local coefficient vector at field position (x, y): init_psf (:154-165) —
 // local[icomp] = sum over spatial terms (m, n) of coef[itot] * dx^m * dy^n,
 // itot running over (term, icomp) with icomp fastest.
 BSGP_HD double psf_local_coef(const PsfModel& M, int icomp, double x, double y) {
-  double v = 0.0;
-  int term = 0;
-  double a1 = 1.0;
-  for (int m = 0; m <= M.sdeg; ++m) {
-    double a2 = 1.0;
-    for (int n = 0; n <= M.sdeg - m; ++n) {
-      v += M.coef[term * M.ncomp + icomp] * a1 * a2;
-      ++term;
-      a2 *= y - M.y_orig;
-    }
-    a1 *= x - M.x_orig;
-  }
-  return v;
+  return psf_local_coef_at(M.coef, M.ncomp, M.sdeg, icomp, x - M.x_orig, y - M.y_orig);
 }
 
-// calc_psf_pix (:52-87) at pixel offset (x, y) with local coefficients `loc`.
-template <class Coef>
-BSGP_HD double psf_pix(const PsfModel& M, const Coef& loc, double x, double y) {
+// The terms of calc_psf_pix (:52-87) at pixel offset (x, y) in its loop order:
+// f(icomp, e, a1, a2) with e = exp(rr_g), a1 = x^m, a2 = y^n.  Shape is
+// anything with cosv, sinv, ax, ay, sig2, ngauss and ldeg (PsfModel, PsfShape).
+// The one statement of the basis: evaluation (psf_pix) multiplies a coefficient
+// in, fitting (bsgp_psffit.hip) takes phi = e * a1 * a2.
+template <class Shape, class F>
+BSGP_HD void psf_terms(const Shape& M, double x, double y, F&& f) {
   const double x1 = M.cosv * x - M.sinv * y;
   const double y1 = M.sinv * x + M.cosv * y;
   double rr = M.ax * x1 * x1 + M.ay * y1 * y1;
-  double pix = 0.0;
   int icomp = 0;
   for (int g = 0; g < M.ngauss; ++g) {
-    const double f = exp(rr);
+    const double e = exp(rr);
     double a1 = 1.0;
     for (int m = 0; m <= M.ldeg; ++m) {
       double a2 = 1.0;
       for (int n = 0; n <= M.ldeg - m; ++n) {
-        pix += loc[icomp] * f * a1 * a2;
+        f(icomp, e, a1, a2);
         ++icomp;
         a2 *= y;
       }
@@ -73,6 +93,15 @@ BSGP_HD double psf_pix(const PsfModel& M, const Coef& loc, double x, double y) {
     }
     rr *= M.sig2;
   }
+}
+
+// calc_psf_pix (:52-87) at pixel offset (x, y) with local coefficients `loc`.
+template <class Coef>
+BSGP_HD double psf_pix(const PsfModel& M, const Coef& loc, double x, double y) {
+  double pix = 0.0;
+  psf_terms(M, x, y, [&](int icomp, double e, double a1, double a2) {
+    pix += loc[icomp] * e * a1 * a2;
+  });
   return pix;
 }
 

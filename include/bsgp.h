@@ -863,6 +863,97 @@ int bsgp_validate_sources(const void* image, int32_t dtype, const double* bkgmap
                           double* stats_out, int32_t* valid_out, int32_t* status_out,
                           void* stream);
 
+/* ---- fitting the DIAPL PSF model ------------------
+ * What the reference leaves to DIAPL's getpsf, an external C program driven by
+ * psf/psf_estimation.bash with the parameters of psf/psf_steps_and_params.MD:
+ * the coefficient file psf_calculate.PSF evaluates.  With the shape parameters
+ * fixed (cos, sin, ax, ay, sigma_inc: getpsf.par's, as DIAPL fixes them for
+ * this step) the model is linear in its coefficients, and the fit is one
+ * weighted least-squares problem per frame with
+ * P = nterm * ncomp unknowns, ncomp = ngauss (ldeg+1)(ldeg+2)/2,
+ * nterm = (sdeg+1)(sdeg+2)/2 (36 for getpsf.par's 2 Gaussians, local degree 2,
+ * spatial degree 1).  Two calls: the moments are the only pass over pixels;
+ * the solve can be repeated on them with other weights or another clipping.
+ * Both are asynchronous; B == 0 or cap == 0 is a no-op that follows no pointer.
+ * Shape parameters are not fitted, stars are neither recentred nor chosen,
+ * there are no per-pixel weights and no neighbour subtraction. */
+#define BSGP_PSFFIT_MAX_COEF 108   /* P (3 Gaussians x 6 local x 6 spatial terms) */
+#define BSGP_PSFFIT_MAX_STARS 4096 /* stars of one frame */
+/* per star */
+#define BSGP_PSFFIT_PARTIAL 1       /* the box leaves the frame: used, with the pixels inside */
+#define BSGP_PSFFIT_BAD_POSITION 2  /* x or y not finite */
+#define BSGP_PSFFIT_NO_OVERLAP 4    /* the box misses the frame */
+#define BSGP_PSFFIT_FEW_PIXELS 8    /* fewer than ncomp fit pixels */
+#define BSGP_PSFFIT_BAD_FLUX 16     /* flux not finite or <= 0 */
+#define BSGP_PSFFIT_BAD_WEIGHT 32   /* weight not finite or <= 0 (the solve) */
+#define BSGP_PSFFIT_CLIPPED 64      /* dropped by a clipping round (the solve) */
+#define BSGP_PSFFIT_EXCLUDED (2 | 4 | 8 | 16 | 32)
+/* per frame */
+#define BSGP_PSFFIT_SINGULAR 128    /* a scaled pivot not finite or <= P * 2^-52 */
+
+/* Per-star moments of the fit.
+ *   image   device [B][H][W], float32 or float64 (dtype = BSGP_DTYPE_*)
+ *   xy      device float64 [B][cap][2]: (x, y) = (column, row), 0-based
+ *   n       device int32 [B]: stars of frame b, or NULL: cap
+ *   model   host: hw, ngauss, ldeg, sdeg, cos, sin, ax, ay, sigma_inc, x_orig,
+ *           y_orig (coeffs and ncoef are not read)
+ *   fitrad  a pixel of the (2hw+1)^2 box about (floor(x + 0.5), floor(y + 0.5))
+ *           that lies in the frame counts when x'^2 + y'^2 <= fitrad^2 for its
+ *           offsets x' = c - x, y' = r - y, its value minus the sky is finite,
+ *           its mask byte is 0 and (has_sat) its value is < sat_level
+ *   flux    device [B][cap], or NULL: the sum of (I - sky) over the fit pixels
+ *           in row-major order
+ *   sky     sky_mode 0: none (NULL); 1: device [B][cap], one value per star;
+ *           2: device float64 [B][H][W] maps
+ *   mask    device bytes [B][H][W], nonzero = skipped, or NULL
+ * With z = (phi_0 .. phi_{ncomp-1}, v), phi_k the terms exp(rr_g) x'^m y'^n of
+ * calc_psf_pix (psf_calculate.py:52-87) in its loop order and
+ * v = (I - sky) / flux, every product rounded and added in pixel order:
+ *   G_out    [B][cap][ncomp (ncomp+1) / 2]  sum phi_i phi_j, packed upper
+ *            triangle, rows in order
+ *   h_out    [B][cap][ncomp]   sum phi_i v
+ *   vv_out   [B][cap]          sum v v
+ *   npix_out [B][cap], flux_out [B][cap] (the flux used), status_out [B][cap]
+ * An excluded star (BSGP_PSFFIT_EXCLUDED) has zero moments.  Rows beyond a
+ * frame's count are zero.
+ * BSGP_ERR_ARG: a NULL array, an unknown dtype or sky_mode, B, cap < 0, H,
+ * W < 1, hw outside 0..255, a degree < 0, ngauss < 1, fitrad not > 0;
+ * BSGP_ERR_UNSUPPORTED: P > BSGP_PSFFIT_MAX_COEF, cap > BSGP_PSFFIT_MAX_STARS,
+ * H * W >= 2^31, B > 65535. */
+int bsgp_psf_fit_moments(const void* image, int32_t dtype, int32_t B, int32_t H, int32_t W,
+                         const double* xy, const int32_t* n, int32_t cap,
+                         const bsgp_psf_model* model, double fitrad, const double* flux,
+                         const double* sky, int32_t sky_mode, const uint8_t* mask, int32_t has_sat,
+                         double sat_level, double* G_out, double* h_out, double* vv_out,
+                         int32_t* npix_out, double* flux_out, int32_t* status_out, void* stream);
+
+/* The coefficients from the moments (getpsf's NSIG_CLIP / NITER rounds
+ * included), one workgroup per frame, no host round trip between rounds.
+ *   xy, n, model, G, h, vv, npix, mstatus   as given to / written by
+ *           bsgp_psf_fit_moments
+ *   weights device [B][cap], or NULL: 1
+ * N = sum w (S S^T) (x) G and b = sum w S (x) h over the active stars in index
+ * order, S the spatial terms (x - x_orig)^m (y - y_orig)^n of init_psf
+ * (psf_calculate.py:140-165); N is scaled by its diagonal, Cholesky-factored and
+ * solved.  Per star rss = max(0, vv - 2 c.h + c.G c) with c the local
+ * coefficients at the star, rms = sqrt(rss / npix).  A clipping round drops
+ * the active stars with rms > median + nsig * 1.4826 * MAD (of the active
+ * stars' rms) and rss > 4096 * 2^-52 * vv, if it drops any and at least
+ * max(nterm, min_stars) remain; the fit is then repeated, at most niter times.
+ *   coef_out   [B][P], term-major as a coefficient file; NaN when singular
+ *   used_out   [B][cap] 0 / 1, status_out [B][cap] (mstatus plus the solve's bits)
+ *   rms_out    [B][cap] of the last fit a star took part in; NaN for a star
+ *              never active and for every star of a singular frame
+ *   frame_out  [B][3]: 0 or BSGP_PSFFIT_SINGULAR, rounds applied, stars used
+ * BSGP_ERR_ARG / BSGP_ERR_UNSUPPORTED as bsgp_psf_fit_moments; niter < 0,
+ * min_stars < 0 or a NaN nsig is BSGP_ERR_ARG. */
+int bsgp_psf_fit_solve(int32_t B, int32_t cap, const int32_t* n, const double* xy,
+                       const bsgp_psf_model* model, const double* G, const double* h,
+                       const double* vv, const int32_t* npix, const int32_t* mstatus,
+                       const double* weights, int32_t niter, double nsig, int32_t min_stars,
+                       double* coef_out, int32_t* used_out, int32_t* status_out, double* rms_out,
+                       int32_t* frame_out, void* stream);
+
 int bsgp_device_synchronize(void);
 const char* bsgp_last_error(void);
 /* The persistent solver's compile-time-geometry path (256 x 256 images on a
