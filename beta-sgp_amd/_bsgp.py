@@ -55,6 +55,12 @@ BSGP_PSFFIT_MAX_COEF, BSGP_PSFFIT_MAX_STARS = 108, 4096
 BSGP_PSFFIT_PARTIAL, BSGP_PSFFIT_BAD_POSITION, BSGP_PSFFIT_NO_OVERLAP = 1, 2, 4
 BSGP_PSFFIT_FEW_PIXELS, BSGP_PSFFIT_BAD_FLUX, BSGP_PSFFIT_BAD_WEIGHT = 8, 16, 32
 BSGP_PSFFIT_CLIPPED, BSGP_PSFFIT_EXCLUDED, BSGP_PSFFIT_SINGULAR = 64, 2 | 4 | 8 | 16 | 32, 128
+# star finding (include/bsgp.h): limits, per-star status bits, the frame's, the sky estimators
+BSGP_STARFIND_MAX_R, BSGP_STARFIND_MAX = 15, 16384
+BSGP_STARFIND_BAD_FLUX, BSGP_STARFIND_OFF_CENTRE = 1, 2
+BSGP_STARFIND_FEW_SKY, BSGP_STARFIND_SKY_OVER_CAP = 4, 8
+BSGP_STARFIND_REJECTED, BSGP_STARFIND_OVER_CAP = 1 | 2 | 4 | 8, 16
+BSGP_STARFIND_BKG_MODE, BSGP_STARFIND_BKG_MEDIAN, BSGP_STARFIND_BKG_MEAN = 0, 1, 2
 # status bits of the background-matched co-add (include/bsgp.h)
 BSGP_COADD_NONFINITE, BSGP_COADD_ISOLATED, BSGP_COADD_NOT_CONVERGED = 1, 2, 4
 # bsgp_convolve2d_ex (include/bsgp.h): kernel size per axis, flags, status bits
@@ -210,6 +216,13 @@ _ENTRY_POINTS = {
                              _dbl, _P, _P, _i32, _P, _i32, _dbl, _P, _P, _P, _P, _P, _P, _P],
     "bsgp_psf_fit_solve": [_i32, _i32, _P, _P, ctypes.POINTER(PsfModel), _P, _P, _P, _P, _P, _P,
                            _i32, _dbl, _i32, _P, _P, _P, _P, _P, _P],
+    "bsgp_star_maps": [_P, _i32, _i32, _i32, _i32, _P, _P, _P, _i32, _dbl, _P, _P, _P],
+    "bsgp_star_peaks": [_P, _i32, _i32, _i32, _i32, _P, _P, _P, _P, _i32, _dbl, _P, _i32, _dbl,
+                        _dbl, _i32, _i32, _P, _P, _P, _P],
+    "bsgp_star_measure": [_P, _i32, _i32, _i32, _i32, _P, _P, _P, _P, _i32, _P, _P, _i32, _dbl,
+                          _dbl, _i32, _dbl, _i32, _i32, _i32, _dbl, _dbl, _P, _P, _P],
+    "bsgp_star_select": [_P, _P, _P, _i32, _i32, _i32, _i32, _i32, _dbl, _i32, _dbl, _dbl, _dbl,
+                         _i32, _P, _P, _P, _P],
 }
 EXPORTED = list(_ENTRY_POINTS) + ["bsgp_last_error", "bsgp_abi_version"]
 

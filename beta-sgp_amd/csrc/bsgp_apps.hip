@@ -3,7 +3,7 @@
 // co-add, FITS pixels, PSF stamps,
 // sky background, convolution, detection, catalogue, local background,
 // deblending, catalogue cross-match, star-stamp metrics, cutouts and selection,
-// source validation, the PSF fit, and the divergences.
+// source validation, the PSF fit, star finding, and the divergences.
 // Each validates its arguments and launches its kernels.
 #include <cmath>
 #include <cstdio>
@@ -756,6 +756,161 @@ int bsgp_psf_fit_solve(int32_t B, int32_t cap, const int32_t* n, const double* x
   HIP_TRY(hipMemsetAsync(status_out, 0, (size_t)B * cap * sizeof(int), s));
   HIP_TRY(hipMemsetAsync(rms_out, 0xff, (size_t)B * cap * sizeof(double), s));
   HIP_TRY(launch_psffit_solve(a, s));
+  return BSGP_OK;
+}
+
+namespace {
+// the support of a star template from the caller's half widths, checked
+int star_support(const int32_t* halfw, int32_t R, signed char* out, int* n) {
+  if (R < 0) return fail(BSGP_ERR_ARG, "R must be >= 0");
+  if (R > kStarMaxR) {
+    char msg[128];
+    snprintf(msg, sizeof msg, "a support of R = %d: a star template reaches at most %d pixels", R,
+             kStarMaxR);
+    return fail(BSGP_ERR_UNSUPPORTED, msg);
+  }
+  if (!halfw) return fail(BSGP_ERR_ARG, "halfw is NULL");
+  int cnt = 0;
+  for (int r = 0; r <= 2 * R; ++r) {
+    if (halfw[r] < 0 || halfw[r] > R) return fail(BSGP_ERR_ARG, "halfw must lie in 0..R");
+    out[r] = (signed char)halfw[r];
+    cnt += 2 * halfw[r] + 1;
+  }
+  *n = cnt;
+  return BSGP_OK;
+}
+
+int star_template(const double* tmpl, const int32_t* halfw, int32_t R, double tt,
+                  StarTemplate* tp) {
+  if (int rc = star_support(halfw, R, tp->halfw, &tp->n)) return rc;
+  if (!tmpl) return fail(BSGP_ERR_ARG, "tmpl is NULL");
+  if (!(tt > 0.0) || !std::isfinite(tt)) return fail(BSGP_ERR_ARG, "tt must be finite and > 0");
+  tp->t = tmpl, tp->R = R, tp->tt = tt, tp->sqrt_tt = std::sqrt(tt);
+  return BSGP_OK;
+}
+}  // namespace
+
+int bsgp_star_maps(const void* image, int32_t dtype, int32_t B, int32_t H, int32_t W,
+                   const uint8_t* mask, const double* tmpl, const int32_t* halfw, int32_t R,
+                   double tt, double* corr_out, double* amp_out, void* stream) {
+  StarMapArgs a{};
+  if (int rc = star_template(tmpl, halfw, R, tt, &a.tp)) return rc;
+  if (int rc = check_dtype(dtype)) return rc;
+  if (int rc = seg_shape(B, H, W)) return rc;
+  if (!image || !corr_out || !amp_out)
+    return fail(BSGP_ERR_ARG, "image / corr_out / amp_out is NULL");
+  a.data = image, a.mask = mask, a.B = B, a.H = H, a.W = W, a.corr = corr_out, a.amp = amp_out;
+  HIP_TRY(launch_star_maps(a, dtype == BSGP_DTYPE_F32, (hipStream_t)stream));
+  return BSGP_OK;
+}
+
+int bsgp_star_peaks(const void* image, int32_t dtype, int32_t B, int32_t H, int32_t W,
+                    const double* corr, const double* amp, const double* tmpl,
+                    const int32_t* halfw, int32_t R, double tt, const double* noise,
+                    int32_t noise_is_map, double c_min, double thresh, int32_t peak_hw,
+                    int32_t cap, int32_t* peaks_out, int32_t* n_out, int32_t* status_out,
+                    void* stream) {
+  StarPeakArgs a{};
+  if (int rc = star_template(tmpl, halfw, R, tt, &a.tp)) return rc;
+  if (int rc = check_dtype(dtype)) return rc;
+  if (int rc = seg_shape(B, H, W)) return rc;
+  if (peak_hw < 0 || peak_hw > 3) return fail(BSGP_ERR_ARG, "peak_hw must lie in 0..3");
+  if (cap < 1) return fail(BSGP_ERR_ARG, "cap must be >= 1");
+  if (cap > kStarMax) {
+    char msg[128];
+    snprintf(msg, sizeof msg, "%d stars: a frame holds at most %d", cap, kStarMax);
+    return fail(BSGP_ERR_UNSUPPORTED, msg);
+  }
+  if (std::isnan(c_min) || std::isnan(thresh)) return fail(BSGP_ERR_ARG, "c_min / thresh is NaN");
+  if (!image || !corr || !amp || !noise)
+    return fail(BSGP_ERR_ARG, "image / corr / amp / noise is NULL");
+  if (!peaks_out || !n_out || !status_out)
+    return fail(BSGP_ERR_ARG, "peaks_out / n_out / status_out is NULL");
+  a.data = image, a.corr = corr, a.amp = amp, a.noise = noise;
+  a.B = B, a.H = H, a.W = W, a.noise_map = noise_is_map ? 1 : 0, a.peak_hw = peak_hw, a.cap = cap;
+  a.nblk = (int)(((int64_t)H * W + kStarChunk - 1) / kStarChunk);
+  a.c_min = c_min, a.thresh = thresh;
+  a.peaks = peaks_out, a.n = n_out, a.status = status_out;
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(hipMemsetAsync(peaks_out, 0, (size_t)B * cap * 2 * sizeof(int), s));
+  // stream-ordered workspace: the call stays asynchronous
+  StreamScratch w(s);
+  const size_t chunks = (size_t)B * a.nblk;
+  if (int rc = w.alloc(chunks * sizeof(int) + chunks * 256)) return rc;
+  a.blk = static_cast<int*>(w.p);
+  a.flag = reinterpret_cast<unsigned char*>(a.blk + chunks);
+  return w.finish(launch_star_peaks(a, dtype == BSGP_DTYPE_F32, s), "star peaks");
+}
+
+int bsgp_star_measure(const void* image, int32_t dtype, int32_t B, int32_t H, int32_t W,
+                      const uint8_t* mask, const double* corr, const double* amp,
+                      const int32_t* halfw, int32_t R, const int32_t* peaks, const int32_t* n,
+                      int32_t cap, double anrad1, double anrad2, int32_t bkg_alg, double sigma,
+                      int32_t maxiters, int32_t min_sky, int32_t has_sat, double sat_level,
+                      double dxy, double* fcols_out, int32_t* icols_out, void* stream) {
+  StarMeasureArgs a{};
+  int nsup = 0;
+  if (int rc = star_support(halfw, R, a.halfw, &nsup)) return rc;
+  if (int rc = check_dtype(dtype)) return rc;
+  if (int rc = seg_shape(B, H, W)) return rc;
+  if (cap < 1) return fail(BSGP_ERR_ARG, "cap must be >= 1");
+  if (cap > kStarMax) return fail(BSGP_ERR_UNSUPPORTED, "cap is above BSGP_STARFIND_MAX");
+  if (!(anrad1 >= 0.0) || !(anrad1 < anrad2) || !std::isfinite(anrad2))
+    return fail(BSGP_ERR_ARG, "the annulus needs 0 <= anrad1 < anrad2");
+  if (anrad2 >= (double)(kStarMaxBox + 1))
+    return fail(BSGP_ERR_UNSUPPORTED, "anrad2 must be below 1025");
+  if (bkg_alg < BSGP_STARFIND_BKG_MODE || bkg_alg > BSGP_STARFIND_BKG_MEAN)
+    return fail(BSGP_ERR_ARG, "bkg_alg must be BSGP_STARFIND_BKG_MODE, _MEDIAN or _MEAN");
+  if (maxiters < 0 || min_sky < 1)
+    return fail(BSGP_ERR_ARG, "maxiters must be >= 0, min_sky >= 1");
+  if (std::isnan(sigma) || std::isnan(dxy) || (has_sat && std::isnan(sat_level)))
+    return fail(BSGP_ERR_ARG, "sigma / dxy / sat_level is NaN");
+  if (!image || !corr || !amp || !peaks || !n)
+    return fail(BSGP_ERR_ARG, "image / corr / amp / peaks / n is NULL");
+  if (!fcols_out || !icols_out) return fail(BSGP_ERR_ARG, "fcols_out / icols_out is NULL");
+  a.data = image, a.mask = mask, a.corr = corr, a.amp = amp, a.peaks = peaks, a.n = n;
+  a.B = B, a.H = H, a.W = W, a.cap = cap, a.R = R, a.box = (int)std::floor(anrad2);
+  a.bkg_alg = bkg_alg, a.maxiters = maxiters, a.min_sky = min_sky, a.has_sat = has_sat ? 1 : 0;
+  a.r1sq = anrad1 * anrad1, a.r2sq = anrad2 * anrad2, a.sigma = sigma, a.sat_level = sat_level;
+  a.dxy2 = dxy * dxy;
+  a.fcols = fcols_out, a.icols = icols_out;
+  hipStream_t s = (hipStream_t)stream;
+  // rows beyond a frame's count: NaN columns (all bits set), zero integers
+  HIP_TRY(hipMemsetAsync(fcols_out, 0xff, (size_t)B * cap * 8 * sizeof(double), s));
+  HIP_TRY(hipMemsetAsync(icols_out, 0, (size_t)B * cap * 4 * sizeof(int), s));
+  HIP_TRY(launch_star_measure(a, dtype == BSGP_DTYPE_F32, s));
+  return BSGP_OK;
+}
+
+int bsgp_star_select(const double* fcols, const int32_t* icols, const int32_t* n, int32_t B,
+                     int32_t cap, int32_t H, int32_t W, int32_t hw, double min_flux,
+                     int32_t has_max_peak, double max_peak, double rat_thresh,
+                     double iso_radius, int32_t npsf_max, int32_t* eligible_out,
+                     int32_t* rank_out, int32_t* selected_out, void* stream) {
+  if (B < 0 || cap < 0) return fail(BSGP_ERR_ARG, "B and cap must be >= 0");
+  if (H < 1 || W < 1) return fail(BSGP_ERR_ARG, "H and W must be >= 1");
+  if (hw < 0 || npsf_max < 0) return fail(BSGP_ERR_ARG, "hw and npsf_max must be >= 0");
+  if (std::isnan(min_flux) || std::isnan(rat_thresh) || std::isnan(iso_radius) ||
+      (has_max_peak && std::isnan(max_peak)))
+    return fail(BSGP_ERR_ARG, "min_flux / max_peak / rat_thresh / iso_radius is NaN");
+  if (cap > kStarMax) return fail(BSGP_ERR_UNSUPPORTED, "cap is above BSGP_STARFIND_MAX");
+  if (B > 65535) return fail(BSGP_ERR_UNSUPPORTED, "B must be at most 65535");
+  if (B == 0 || cap == 0) return BSGP_OK;
+  if (!fcols || !icols) return fail(BSGP_ERR_ARG, "fcols / icols is NULL");
+  if (!eligible_out || !rank_out || !selected_out)
+    return fail(BSGP_ERR_ARG, "eligible_out / rank_out / selected_out is NULL");
+  StarSelectArgs a{};
+  a.fcols = fcols, a.icols = icols, a.n = n;
+  a.B = B, a.cap = cap, a.H = H, a.W = W, a.hw = hw, a.has_max_peak = has_max_peak ? 1 : 0;
+  a.npsf_max = npsf_max, a.min_flux = min_flux, a.max_peak = max_peak;
+  a.rat_thresh = rat_thresh, a.iso2 = iso_radius * iso_radius;
+  a.eligible = eligible_out, a.rank = rank_out, a.selected = selected_out;
+  hipStream_t s = (hipStream_t)stream;
+  const size_t rows = (size_t)B * cap;
+  HIP_TRY(hipMemsetAsync(eligible_out, 0, rows * sizeof(int), s));
+  HIP_TRY(hipMemsetAsync(rank_out, 0xff, rows * sizeof(int), s));
+  HIP_TRY(hipMemsetAsync(selected_out, 0, rows * sizeof(int), s));
+  HIP_TRY(launch_star_select(a, s));
   return BSGP_OK;
 }
 

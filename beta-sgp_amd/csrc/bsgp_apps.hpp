@@ -1,8 +1,8 @@
 // bsgp_apps.hpp — the application stages' argument blocks, limits and launch
 // declarations: what their kernel units (bsgp_tiles, bsgp_coadd, bsgp_psf,
 // bsgp_background, bsgp_segment, bsgp_convolve, bsgp_localbkg, bsgp_match,
-// bsgp_deblend, bsgp_stamps, bsgp_starstamps, bsgp_validate, bsgp_psffit .hip) share with the C-ABI host
-// layer (bsgp_apps.hip).  Nothing of the solver.  Not part of the public interface.
+// bsgp_deblend, bsgp_stamps, bsgp_starstamps, bsgp_validate, bsgp_psffit, bsgp_starfind .hip) share
+// with the C-ABI host layer (bsgp_apps.hip).  Nothing of the solver.  Not part of the public interface.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -298,5 +298,61 @@ struct PsfFitSolveArgs {
 int psffit_chunk(int ncomp);
 hipError_t launch_psffit_moments(PsfFitMomentArgs a, int f32, hipStream_t s);
 hipError_t launch_psffit_solve(PsfFitSolveArgs a, hipStream_t s);
+// ---- star finding (bsgp_starfind.hip) ---------------
+constexpr int kStarMaxR = BSGP_STARFIND_MAX_R;  // the tile, its halo and the template: 30 KiB of LDS
+constexpr int kStarMax = BSGP_STARFIND_MAX;     // stars of one frame
+constexpr int kStarChunk = 2048;                // pixels one workgroup numbers in the compaction
+constexpr int kStarMaxBox = 1024;               // floor(anrad2): the annulus' box stays an int count
+// F1 (by value: scalar loads): row dy of the support is |dx| <= halfw[dy + R]
+struct StarTemplate {
+  const double* t;  // [n] on the device, the support's row-major order
+  int R, n;
+  double tt, sqrt_tt;
+  signed char halfw[2 * kStarMaxR + 1];
+};
+struct StarMapArgs {
+  const void* data;           // [B][H][W] float32 or float64
+  const unsigned char* mask;  // [B][H][W] bytes, nonzero = masked, or nullptr
+  StarTemplate tp;
+  int B, H, W;
+  double *corr, *amp;  // [B][H][W]
+};
+struct StarPeakArgs {
+  const void* data;          // [B][H][W] float32 or float64
+  const double *corr, *amp;  // [B][H][W] as k_star_maps wrote them
+  const double* noise;       // [B], or [B][H][W] when noise_map
+  StarTemplate tp;
+  int B, H, W, noise_map, peak_hw, cap, nblk;  // nblk: chunks of kStarChunk pixels per frame
+  double c_min, thresh;
+  unsigned char* flag;  // workspace [B][nblk][256]: the candidate bits of a lane's 8 pixels
+  int* blk;             // workspace [B][nblk]: candidates per chunk, then their scan
+  int* peaks;           // [B][cap][2]: ic, ir
+  int *n, *status;      // [B]
+};
+struct StarMeasureArgs {
+  const void* data;           // [B][H][W] float32 or float64
+  const unsigned char* mask;  // [B][H][W] bytes, or nullptr
+  const double *corr, *amp;   // [B][H][W]
+  const int* peaks;           // [B][cap][2]
+  const int* n;               // [B]
+  int B, H, W, cap, R, box, bkg_alg, maxiters, min_sky, has_sat;  // box: floor(anrad2)
+  double r1sq, r2sq, sigma, sat_level, dxy2;
+  signed char halfw[2 * kStarMaxR + 1];
+  double* fcols;  // [B][cap][8]: x, y, flux, bkg, peak, corr, amp, fwhm (NaN first)
+  int* icols;     // [B][cap][4]: ic, ir, nsat, status (zeroed first)
+};
+struct StarSelectArgs {
+  const double* fcols;  // [B][cap][8]
+  const int* icols;     // [B][cap][4]
+  const int* n;         // [B], or nullptr: cap
+  int B, cap, H, W, hw, has_max_peak, npsf_max;
+  double min_flux, max_peak, rat_thresh, iso2;
+  int *eligible, *rank, *selected;  // [B][cap] (0, -1, 0 first)
+};
+int star_annulus_pixels(double r1sq, double r2sq, int box);  // of an annulus inside the frame
+hipError_t launch_star_maps(const StarMapArgs& a, int f32, hipStream_t s);
+hipError_t launch_star_peaks(const StarPeakArgs& a, int f32, hipStream_t s);
+hipError_t launch_star_measure(const StarMeasureArgs& a, int f32, hipStream_t s);
+hipError_t launch_star_select(const StarSelectArgs& a, hipStream_t s);
 
 }  // namespace bsgp

@@ -490,8 +490,10 @@ def fit_psf(image, positions, hw=15, ngauss=2, ldeg=2, sdeg=1, fwhm=None, shape=
     expansion: (W / 2, H / 2) by default.
 
     Not done: the shape parameters are not fitted, the stars are not
-    recentred, chosen or cleaned of neighbours, and pixels carry no noise
-    weights.  Returns a :class:`PSFFit`; a singular frame warns and has no
+    recentred or cleaned of neighbours, and pixels carry no noise weights.
+    Choosing the stars is ``starfind.select_psf_stars``, whose
+    ``StarList.psf_inputs(sel)`` are this function's ``positions``, ``flux``
+    and ``background``.  Returns a :class:`PSFFit`; a singular frame warns and has no
     ``psf``."""
     torch = _B.torch
     ishape = tuple(image.shape)

@@ -954,6 +954,120 @@ int bsgp_psf_fit_solve(int32_t B, int32_t cap, const int32_t* n, const double* x
                        double* coef_out, int32_t* used_out, int32_t* status_out, double* rms_out,
                        int32_t* frame_out, void* stream);
 
+/* ---- finding and measuring a frame's stars --------
+ * What the reference leaves to DIAPL's sfind and fwhmm (psf/psf_estimation.bash,
+ * psf/psf_steps_and_params.MD) and the star choice of getpsf: from a frame to
+ * the rows of a .coo file (x y approx_flux local_bkg_level num_saturated) and to
+ * the PSF stars bsgp_psf_fit_moments takes.  DIAPL's source is not part of the
+ * reference, so the rule is this library's own, modelled on the published
+ * parameter files and restated in numpy in tests/starfind_ref.py.  Float64
+ * arithmetic on float32 or float64 frames, every product and sum rounded, no
+ * floating-point atomics: a batch gives each frame the bits it gets alone.
+ * All four calls are asynchronous.
+ *
+ * The template (F1) is built by the caller and shared by all calls: for
+ * rap = aprad * fwhm and R = floor(rap) <= BSGP_STARFIND_MAX_R the support is
+ * the offsets |dy| <= R, |dx| <= halfw[dy + R] (the dx with dx^2 + dy^2 <=
+ * rap^2) in row-major order, n of them; tmpl[n] on the device holds
+ * t = g - mean(g), g = exp(-(dx^2 + dy^2) / (2 sigma^2)), and tt = sum t^2.
+ *   halfw   HOST int32 [2R + 1], each in 0..R */
+#define BSGP_STARFIND_MAX_R 15
+#define BSGP_STARFIND_MAX 16384 /* stars of one frame */
+/* per star (icols' status) */
+#define BSGP_STARFIND_BAD_FLUX 1     /* aperture flux not finite or <= 0 */
+#define BSGP_STARFIND_OFF_CENTRE 2   /* brightest pixel farther than dxy from (x, y) */
+#define BSGP_STARFIND_FEW_SKY 4      /* fewer than min_sky annulus values */
+#define BSGP_STARFIND_SKY_OVER_CAP 8 /* more than BSGP_LOCALBKG_MAX annulus values */
+#define BSGP_STARFIND_REJECTED (1 | 2 | 4 | 8)
+/* per frame (bsgp_star_peaks' status_out) */
+#define BSGP_STARFIND_OVER_CAP 16 /* more candidates than cap: the first cap are kept */
+#define BSGP_STARFIND_BKG_MODE 0
+#define BSGP_STARFIND_BKG_MEDIAN 1
+#define BSGP_STARFIND_BKG_MEAN 2
+
+/* F2, F3: the maps.  Pixel p is valid when its whole support lies in the
+ * frame and every support pixel is finite and unmasked; otherwise both maps
+ * hold NaN at p.  Over the support in its order s1 = sum I, s2 = sum I I,
+ * st = sum t I; var = s2 - s1 s1 / n; amp = st / tt;
+ * corr = st / sqrt(tt var) if var > 0, else 0.
+ *   image   device [B][H][W], float32 or float64 (dtype = BSGP_DTYPE_*)
+ *   mask    device bytes [B][H][W], nonzero = masked, or NULL
+ *   corr_out, amp_out   device float64 [B][H][W]
+ * BSGP_ERR_ARG: a NULL array, an unknown dtype, R < 0, a halfw outside 0..R,
+ * tt not > 0; BSGP_ERR_UNSUPPORTED: R > BSGP_STARFIND_MAX_R, H * W >= 2^31,
+ * B > 65535. */
+int bsgp_star_maps(const void* image, int32_t dtype, int32_t B, int32_t H, int32_t W,
+                   const uint8_t* mask, const double* tmpl, const int32_t* halfw, int32_t R,
+                   double tt, double* corr_out, double* amp_out, void* stream);
+
+/* F4, F5: the candidates.  p is one when it is valid (amp is not NaN),
+ * corr >= c_min, st >= (thresh * noise(p)) * sqrt(tt) (st added again from the
+ * frame exactly as the maps added it) and amp(p) is the maximum of the
+ * (2 peak_hw + 1)^2 window over valid pixels, strictly above those earlier in
+ * raster order and >= those later.  Numbered in raster order per frame.
+ *   noise      device float64 [B] (noise_is_map == 0) or [B][H][W]
+ *   peaks_out  device int32 [B][cap][2]: column, row of candidate r of frame b
+ *   n_out      device int32 [B]: min(candidates, cap)
+ *   status_out device int32 [B]: 0 or BSGP_STARFIND_OVER_CAP
+ * BSGP_ERR_ARG as bsgp_star_maps, and peak_hw outside 0..3, cap < 1, a NaN
+ * c_min or thresh; BSGP_ERR_UNSUPPORTED: cap > BSGP_STARFIND_MAX. */
+int bsgp_star_peaks(const void* image, int32_t dtype, int32_t B, int32_t H, int32_t W,
+                    const double* corr, const double* amp, const double* tmpl,
+                    const int32_t* halfw, int32_t R, double tt, const double* noise,
+                    int32_t noise_is_map, double c_min, double thresh, int32_t peak_hw,
+                    int32_t cap, int32_t* peaks_out, int32_t* n_out, int32_t* status_out,
+                    void* stream);
+
+/* F6 to F8: one workgroup per candidate.
+ * Sky: the pixels with anrad1^2 <= dx^2 + dy^2 <= anrad2^2 about the peak
+ * pixel (ic, ir) that lie in the frame, are finite, unmasked and (has_sat)
+ * < sat_level, sorted and sigma-clipped (median -+ sigma * std, at most
+ * maxiters rounds; the local background's L4) and reduced by bkg_alg: MODE is
+ * the local background's L5 (mean if std == 0, 2.5 median - 1.5 mean if
+ * |mean - median| / std < 0.3, else median), MEDIAN and MEAN the clipped ones.
+ * Fewer than min_sky values: bkg NaN and FEW_SKY; more than BSGP_LOCALBKG_MAX:
+ * bkg NaN and SKY_OVER_CAP.
+ * Aperture: the template's support about (ic, ir) with J = I - bkg; each
+ * support row left to right, then the row sums top to bottom:
+ * F = sum J, Sx = sum dx J, Sy = sum dy J, Sxx = sum (dx dx) J, Syy, Sxy;
+ * x = ic + Sx / F, y = ir + Sy / F,
+ * fwhm = 2 sqrt(2 ln 2) sqrt(((Sxx / F - (Sx / F)^2) + (Syy / F - (Sy / F)^2)) / 2),
+ * NaN unless the argument is > 0; peak = max I - bkg, the brightest pixel the
+ * first maximum in raster order; nsat counts support pixels >= sat_level.
+ * BAD_FLUX: F not finite or <= 0; OFF_CENTRE: the brightest pixel's squared
+ * distance from (x, y) exceeds dxy^2.
+ *   peaks, n   as bsgp_star_peaks wrote them
+ *   fcols_out  device float64 [B][cap][8]: x, y, flux, bkg, peak, corr, amp, fwhm
+ *   icols_out  device int32 [B][cap][4]: ic, ir, nsat, status
+ * Rows beyond a frame's count are NaN / 0.
+ * BSGP_ERR_ARG: a NULL array, not 0 <= anrad1 < anrad2, an unknown bkg_alg,
+ * maxiters < 0, min_sky < 1, a NaN sigma or dxy; BSGP_ERR_UNSUPPORTED:
+ * anrad2 >= 1025, and as above. */
+int bsgp_star_measure(const void* image, int32_t dtype, int32_t B, int32_t H, int32_t W,
+                      const uint8_t* mask, const double* corr, const double* amp,
+                      const int32_t* halfw, int32_t R, const int32_t* peaks, const int32_t* n,
+                      int32_t cap, double anrad1, double anrad2, int32_t bkg_alg, double sigma,
+                      int32_t maxiters, int32_t min_sky, int32_t has_sat, double sat_level,
+                      double dxy, double* fcols_out, int32_t* icols_out, void* stream);
+
+/* F9: the PSF stars.  A star without a BSGP_STARFIND_REJECTED bit ("kept") is
+ * eligible when flux >= min_flux, nsat == 0, (has_max_peak) peak <= max_peak,
+ * the (2 hw + 1)^2 box about (floor(x + 0.5), floor(y + 0.5)) lies in the
+ * frame, and no other kept star t with flux_t >= rat_thresh * flux has
+ * dx dx + dy dy <= iso_radius^2.  Its rank is the number of eligible stars
+ * that are brighter, or equally bright with a smaller index; it is selected
+ * when the rank is below npsf_max.
+ *   fcols, icols   as bsgp_star_measure wrote them; n device [B] or NULL: cap
+ *   eligible_out, rank_out (-1: not eligible), selected_out   device int32 [B][cap]
+ * BSGP_ERR_ARG: a NULL array, B or cap < 0, H, W < 1, hw < 0, npsf_max < 0, a
+ * NaN among the numbers; BSGP_ERR_UNSUPPORTED: cap > BSGP_STARFIND_MAX,
+ * B > 65535.  B == 0 or cap == 0 is a no-op. */
+int bsgp_star_select(const double* fcols, const int32_t* icols, const int32_t* n, int32_t B,
+                     int32_t cap, int32_t H, int32_t W, int32_t hw, double min_flux,
+                     int32_t has_max_peak, double max_peak, double rat_thresh,
+                     double iso_radius, int32_t npsf_max, int32_t* eligible_out,
+                     int32_t* rank_out, int32_t* selected_out, void* stream);
+
 int bsgp_device_synchronize(void);
 const char* bsgp_last_error(void);
 /* The persistent solver's compile-time-geometry path (256 x 256 images on a
